@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: Mpixels/s encode (UYVY -> DXT5-YCoCg, 4K) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: either under python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ..., or as plain
      `python bench.py --gpus N`, which then starts the N ranks itself the same way)
+
+A plain run sets up, warms up, times the K steps and prints the line (the driver contract fields, `config` and `roofline`); nothing else.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path computed as DIR/<name>.npy (float32; float64 for stream
+lengths), whole where it fits, else a fixed seeded sample, at most 64 MB in all (dump_outputs()).  The inputs are seeded: the same
+arguments give the same inputs on every run, so that two builds can be compared output for output.
+--full adds the legs below (parity_check, configs, e2e, cpu_baseline, cpu_reference), each after the timed region; --no-* switch them off
+one by one.
 
 One "step" = passes of the hot path (fused UYVY unpack + YUV->RGB + RGB->YCoCg + DXT5 block encode,
 ug_hip_dxt_encode_batch: one launch = `--frames` = 16 distinct synthetic 3840x2160 UYVY frames, BASELINE.json
@@ -14,12 +21,13 @@ with no collective (weak scaling: every rank encodes its own batches).
 Prints ONE JSON line (rank 0) with the driver contract fields plus
   roofline     -- algorithmic bytes (3.0 B/px: 2 read + 1 written) x pixels per
                   launch / average launch duration measured with HIP events on the launch stream;
+and, with --full only:
   e2e          -- the PCIe-inclusive rate (pinned host -> H2D -> kernel -> D2H, 3 frames in flight per GPU, all ranks at once) for
                   8K UYVY (the target's literal configuration), 8K v210 and 4K UYVY: fps per GPU and in total, PCIe GB/s -- reported
                   beside `value`, never as `value`;
   cpu_baseline -- the CPU oracle (oracle/dxt_oracle.c, "port": the reference has no CPU DXT encoder)
                   timed on this box's host cores on a bounded sample (rank 0, at every N).
-Additive keys of the default N = 1 line (`value` / `roofline` are computed exactly as before, and first):
+Additive keys of the default N = 1 line with --full (`value` / `roofline` are computed exactly as before, and first):
   parity_check -- frame 0 of the timed batch, as the timed kernel left it, compared byte for byte with oracle/dxt_oracle.c AFTER the timed region;
   configs      -- the other BASELINE configurations under the same clock: ~1 s of timed launches each (HIP events on the launch stream) ->
                   ms_per_launch, frac of 8 TB/s, launches_timed (the code paths of --workload);
@@ -443,6 +451,46 @@ def load_pmc(pmc_key, root: str = ROOT) -> dict:
     return pmc
 
 
+DUMP_MAX_ELEMS = 12 << 20   # --dump-outputs: 12 Mi float32 values in all (48 MiB + headers, under 64 MB)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(ws: dict, launches_per_step: int, out_dir: str) -> dict:
+    """--dump-outputs: what the timed launches handed their caller, as `out_dir`/<name>.npy, 1-D float32 (the values are bytes / int16
+    coefficients, exact in float32).  DXT: the blocks of every resident batch; JPEG420: the Y / Cb / Cr coefficients of the last launch;
+    JPEGENC: the streams of the last call back to back, and their lengths (float64).  An array that does not fit the common budget of
+    DUMP_MAX_ELEMS values is sampled: one position drawn (seeded) in each of k equal slices of it, the same positions on every run.
+    Returns {name: [values written, values in the output]}."""
+    torch.cuda.synchronize()
+    out_name = ws["out_name"]
+    extra = {}
+    if out_name in ("DXT5", "DXT1"):
+        arrays = {f"{out_name.lower()}_blocks": ws["dst"].reshape(-1)}
+    elif out_name == "JPEG420":
+        arrays = dict(zip(("coef_y", "coef_cb", "coef_cr"), (c.reshape(-1) for c in ws["coef"])))
+    else:
+        b = (launches_per_step - 1) % ws["B"]            # the batch of the last call of the step
+        lens = [int(ws["lens"][f]) for f in range(ws["F"])]
+        arrays = {"jpeg_streams": torch.cat([ws["jout"][b, f, :n] for f, n in enumerate(lens)])}
+        extra["jpeg_stream_lens"] = np.asarray(lens, np.float64)
+    total = sum(int(t.numel()) for t in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for i, (name, t) in enumerate(arrays.items()):
+        n = int(t.numel())
+        k = min(n, max(1, n * DUMP_MAX_ELEMS // total))
+        if k < n:
+            step = n // k
+            pos = np.arange(k, dtype=np.int64) * step + np.random.Generator(np.random.PCG64(DUMP_SEED + i)).integers(0, step, k)
+            t = t[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+        written[name] = [k, n]
+    for name, a in extra.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = [a.size, a.size]
+    return written
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -452,6 +500,10 @@ def main() -> None:
     ap.add_argument("--batches", type=int, default=4, help="distinct resident batches the launches of a step cycle through")
     ap.add_argument("--launches-per-step", type=int, default=0, help="kernel launches per step; 0 = as many as make a step >= 50 ms of GPU work")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="4k-uyvy")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed as DIR/<name>.npy (float32, at most 64 MB; rank 0)")
+    ap.add_argument("--full", action="store_true", help="also run the legs after the timed region: parity_check, configs, e2e, cpu_baseline, "
+                    "cpu_reference (each can be switched off with its --no-* option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive leg")
     ap.add_argument("--e2e-seconds", type=float, default=2.0)
@@ -550,20 +602,22 @@ def main() -> None:
     # barrier + synchronize on both sides of exactly K steps, MAX over ranks (ultragrid_amd/shard.py)
     wall = shard.timed_steps(timed_step, args.steps, torch.cuda.synchronize, dist, device=coll_dev)
     kern_ms = ev0.elapsed_time(ev1) / (args.steps * L)   # average launch duration (back-to-back launches on one stream)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(ws, L, args.dump_outputs)
 
-    # ---- additive legs, all after the timed region ----
+    # ---- additive legs (--full), all after the timed region ----
     parity = None
-    if rank == 0 and not args.no_parity_check and out_name in ("DXT5", "DXT1"):
+    if args.full and rank == 0 and not args.no_parity_check and out_name in ("DXT5", "DXT1"):
         parity = parity_check(ws)
     ws.clear()
     launch = None   # (with it go the resident batches: the closure held them)
     torch.cuda.empty_cache()
     configs = None
-    if world == 1 and not args.no_configs and args.workload == "4k-uyvy":   # the default N = 1 line only: at N > 1 nothing is added to what the ranks wait for
+    if args.full and world == 1 and not args.no_configs and args.workload == "4k-uyvy":   # the default N = 1 line only: at N > 1 nothing is added to what the ranks wait for
         configs = other_configs(rank, args.configs_seconds)
 
     e2e = None
-    if not args.no_e2e and out_name in ("DXT5", "DXT1"):
+    if args.full and not args.no_e2e and out_name in ("DXT5", "DXT1"):
         torch.cuda.empty_cache()
         # 8k-uyvy = the north star's literal target configuration (>= 60 fps 8K UYVY -> DXT5-YCoCg on one MI355X)
         e2e = e2e_leg(["8k-uyvy", "8k-v210", "4k-uyvy"], rank, dist, coll_dev, args.e2e_seconds)
@@ -646,7 +700,7 @@ def main() -> None:
             out["config"]["dist"] = {"backend": args.dist_backend + (" (RCCL)" if args.dist_backend == "nccl" else ""), "world": world,
                                      "collectives": "barrier + all_reduce(MAX) around the timed steps, all_reduce(MAX) of the step size, all_gather of per-rank "
                                                     "e2e rates; on " + coll_dev + " tensors; never frame data"}
-        if not args.no_cpu_baseline and out_name not in ("JPEG420", "JPEGENC"):   # rank 0, at every world size (the other ranks wait in destroy_process_group)
+        if args.full and not args.no_cpu_baseline and out_name not in ("JPEG420", "JPEGENC"):   # rank 0, at every world size (the other ranks wait in destroy_process_group)
             out["cpu_baseline"] = cpu_baseline(host[0], wl["fmt"], W, H, out=out_name)
             try:
                 ref = cpu_reference(wl["fmt"], W, H)

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,7 +23,7 @@ def _line(out):
 
 def test_single_gpu_line(hip):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--launches-per-step", "8", "--e2e-seconds", "0.3",
-                        "--configs-seconds", "0.25", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--configs-seconds", "0.25", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout + r.stderr
     d = _line(r.stdout)
     # the additive keys of round 5: an in-run oracle check of the timed kernel's output, every other BASELINE configuration
@@ -66,13 +67,34 @@ def test_single_gpu_line(hip):
     assert "dist" not in d["config"]
 
 
+def test_plain_line_and_dumped_outputs(hip, tmp_path):
+    """Without --full the line carries the contract fields, `config` and `roofline` only; --dump-outputs writes the timed path's output
+    (a seeded sample of the DXT5 blocks of every resident batch) as float32, under 64 MB, the same whatever the number of steps."""
+    dumps = []
+    for steps, lps in ((2, 8), (3, 4)):
+        out = tmp_path / f"steps{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--launches-per-step", str(lps), "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout + r.stderr
+        d = _line(r.stdout)
+        assert REQUIRED <= set(d) and d["steps"] == steps and d["ms_per_step"] > 0 and d["config"]["launches_per_step"] == lps
+        assert not {"parity_check", "configs", "e2e", "cpu_baseline", "cpu_reference"} & set(d), sorted(d)
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["dxt5_blocks.npy"], files
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 10**6
+        a = np.load(out / "dxt5_blocks.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and a.size == 12 << 20 and a.min() >= 0 and a.max() <= 255 and len(np.unique(a)) > 200
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
 def test_rccl_group_at_world_size_one(hip):
     """the `nccl` (= RCCL) branch of bench.py -- init_process_group with a device id, barrier, all_reduce(MAX) of the step size
     and of the wall time, all_gather of the e2e rates, all on cuda tensors -- runs here at world size 1, so that the driver's 8-GPU run is
     not the first time any of it executes; and the CPU baseline is in the line whenever a group is up."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--launches-per-step", "8", "--e2e-seconds", "0.3",
-                        "--force-dist"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--force-dist", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     d = _line(r.stdout)
     assert d["n_gpus"] == 1 and d["config"]["dist"]["backend"].startswith("nccl") and d["config"]["dist"]["world"] == 1
@@ -98,7 +120,7 @@ def test_two_ranks_on_one_gpu_smoke(hip):
     port = 29600 + os.getpid() % 1000
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
                         os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--launches-per-step", "8", "--e2e-seconds", "0.3",
-                        "--dist-backend", "gloo", "--all-ranks-on-device0"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--dist-backend", "gloo", "--all-ranks-on-device0", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     d = _line(r.stdout)
     assert d["n_gpus"] == 2 and d["cpu_baseline"]["value"] > 0   # rank 0 times the CPU oracle at every world size

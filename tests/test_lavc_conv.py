@@ -158,17 +158,34 @@ def test_color_coefficient_tables():
             assert list(got) == want, (cs, depth)
 
 
-def test_compute_color_coeffs():
-    """ug_hip_compute_color_coeffs == compute_color_coeffs of the compiled reference (color_space.c:193-197), incl. the BT.601 / 709 / 2020 weights"""
+COEFF_WEIGHTS = [(0.299, 0.114), (0.2126, 0.0722), (0.2627, 0.0593), (0.212, 0.087), (0.3, 0.11)]
+COEFF_DEPTHS = (0, 8, 10, 12, 16)
+
+
+def ref_compute_color_coeffs(kr, kb, depth):
+    """compute_color_coeffs of the compiled reference (oracle/_ref/libugref.so), as the 14 fields of its struct"""
     from oracle import pyoracle as O
-    from ultragrid_amd import lib
     r = O.ref()
     r.compute_color_coeffs.restype = O._RefCoeffs
     r.compute_color_coeffs.argtypes = [C.c_double, C.c_double, C.c_int]
-    for kr, kb in [(0.299, 0.114), (0.2126, 0.0722), (0.2627, 0.0593), (0.212, 0.087), (0.3, 0.11)]:
-        for depth in (0, 8, 10, 12, 16):
-            want = r.compute_color_coeffs(kr, kb, depth)
-            want = [getattr(want, n) for n, _ in O._RefCoeffs._fields_]
+    want = r.compute_color_coeffs(kr, kb, depth)
+    return [getattr(want, n) for n, _ in O._RefCoeffs._fields_]
+
+
+def test_compute_color_coeffs():
+    """ug_hip_compute_color_coeffs == compute_color_coeffs of the compiled reference (color_space.c:193-197), incl. the BT.601 / 709 / 2020 weights:
+    against committed vectors (tests/golden/color_coeffs_ref.npz, made by tests/golden/make_color_coeffs_golden.py from the compiled reference),
+    and against the compiled reference itself where oracle/_ref is built"""
+    from oracle import pyoracle as O
+    from ultragrid_amd import lib
+    g = np.load(os.path.join(HERE, "golden", "color_coeffs_ref.npz"))
+    assert g["weights"].tolist() == [list(w) for w in COEFF_WEIGHTS] and g["depths"].tolist() == list(COEFF_DEPTHS)
+    live = os.path.exists(O._REF_PATH)
+    for i, (kr, kb) in enumerate(COEFF_WEIGHTS):
+        for j, depth in enumerate(COEFF_DEPTHS):
+            want = g["coeffs"][i, j].tolist()
+            if live:
+                assert ref_compute_color_coeffs(kr, kb, depth) == want, (kr, kb, depth)
             got = (C.c_int * 14)()
             assert lib.load().ug_hip_compute_color_coeffs(kr, kb, depth, got) == 0
             assert list(got) == want, (kr, kb, depth)
@@ -189,23 +206,23 @@ def test_reference_has_every_row_we_claim():
 
 
 def test_conversion_tables_are_covered():
-    """every row of the reference's two conversion tables (read from its source here, where /root/reference exists) is either
-    supported by the library or on the short list of rows deliberately left out"""
-    import re
+    """every row of the reference's two conversion tables (tests/golden/reference_tables.json, checked against its source where that exists)
+    is either supported by the library or on the short list of rows deliberately left out"""
+    import sys
     from ultragrid_amd import lib
     base = "/root/reference/src/libavcodec/"
-    if not os.path.exists(base):
-        pytest.skip("no /root/reference here")
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    import make_reference_tables
+    tables = make_reference_tables.tables(os.path.dirname(os.path.dirname(base)))
     L = lib.load()
 
     def name(f):
         return {"XV30": "xv30le", "Y210": "y210le", "Y212": "y212le", "AYUV64": "ayuv64le", "AYUV64LE": "ayuv64le"}.get(f, f.lower())
-    rows = re.findall(r"\{ *(\w+), *AV_PIX_FMT_(\w+), *(\w+) *\}", open(base + "to_lavc_vid_conv.c").read())
-    rows = [r for r in rows if r[0] != "VIDEO_CODEC_NONE"]
-    missing = {(c, f) for c, f, _ in rows if not L.ug_hip_uv_to_av_supported(c.encode(), name(f).encode())}
+    rows = tables["to_lavc"]
+    missing = {(c, f) for c, f in rows if not L.ug_hip_uv_to_av_supported(c.encode(), name(f).encode())}
     assert len(rows) == 57 and not missing, missing
-    rows = re.findall(r"\{ *AV_PIX_FMT_(\w+), *(\w+),\s*(\w+),\s*(\w+) *\}", open(base + "from_lavc_vid_conv.c").read())
-    missing = {(f, c) for f, c, _, _ in rows if not L.ug_hip_av_to_uv_supported(name(f).encode(), c.encode())}
+    rows = tables["from_lavc"]
+    missing = {(f, c) for f, c in rows if not L.ug_hip_av_to_uv_supported(name(f).encode(), c.encode())}
     assert len(rows) == 105, len(rows)
     assert missing == {("Y212", "Y216"), ("Y210", "Y216"), ("AYUV64", "UYVY"), ("VDPAU", "HW_VDPAU"), ("DRM_PRIME", "DRM_PRIME")}, missing
 

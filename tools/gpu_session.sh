@@ -6,9 +6,9 @@
 #   tests            the whole GPU suite
 #   tests:<expr>     pytest -m gpu -k <expr>
 #   runtime          tests/test_runtime_conventions.py on the product modules, then the same under the ASan / TSan builds of harness + modules
-#   bench            the default bench.py line
-#   bench:<workload> bench.py --workload <workload> --no-e2e
-#   trace            rocprofv3 --kernel-trace --stats of the default bench command (no CPU legs) -> kernel_trace.txt
+#   bench            the default bench.py line with every leg (--full)
+#   bench:<workload> bench.py --workload <workload> --full --no-e2e
+#   trace            rocprofv3 --kernel-trace --stats of the default bench command with --full but no CPU legs -> kernel_trace.txt
 #   pmc              rocprofv3 --pmc passes of the five bench workloads' kernels -> profiles-ready summaries + pmc_traffic.json (what bench.py quotes as `traffic`)
 #   jpeg             the JPEG encoder's rates in every call form (tools/bench_jpeg_batch.py), kernel trace and phase clock
 #   tables           the per-kernel, decoder, pixel-format and de-interlace tables (2.4 GB of rotating buffers per row)
@@ -26,10 +26,10 @@ for step in "$@"; do
     runtime)
       timeout 1500 python -m pytest tests/test_runtime_conventions.py -q --maxfail=20 2>&1 | tail -40 > $OUT/runtime_plain.log; tail -5 $OUT/runtime_plain.log
       timeout 1500 python -m pytest tests/test_runtime_conventions.py -m gpu -q -k "asan or tsan" --maxfail=40 2>&1 | tail -120 > $OUT/runtime_sanitized.log; tail -8 $OUT/runtime_sanitized.log ;;
-    bench)    python bench.py > $OUT/bench_line.json 2> $OUT/bench.err; cut -c1-400 $OUT/bench_line.json; tail -3 $OUT/bench.err ;;
-    bench:*)  wl=${step#bench:}; python bench.py --workload $wl --no-e2e > $OUT/bench_$wl.json 2>> $OUT/bench.err; cut -c1-300 $OUT/bench_$wl.json ;;
+    bench)    python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err; cut -c1-400 $OUT/bench_line.json; tail -3 $OUT/bench.err ;;
+    bench:*)  wl=${step#bench:}; python bench.py --workload $wl --full --no-e2e > $OUT/bench_$wl.json 2>> $OUT/bench.err; cut -c1-300 $OUT/bench_$wl.json ;;
     trace)
-      ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- python $ROOT/bench.py --no-cpu-baseline --no-e2e > $OUT/trace.log 2>&1 )
+      ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- python $ROOT/bench.py --full --no-cpu-baseline --no-e2e > $OUT/trace.log 2>&1 )
       python tools/pmc_summary.py $(find $OUT/trace -name "*.db") 2>&1 | sed "s#$ROOT/##" > $OUT/kernel_trace.txt; head -6 $OUT/kernel_trace.txt | cut -c1-170
       grep "^{" $OUT/trace.log | tail -1 > $OUT/trace_bench_line.json; rm -rf $OUT/trace ;;
     pmc-jpeg)  # the two JPEG workloads only
