@@ -439,7 +439,10 @@ int ug_hip_uyvy_to_jpeg42x_coeffs_batch(int subsampling, const void *src_dev, in
  * 0.08 / 0.16 ms with restart intervals (profiles/r06_encode_no_restart.txt). */
 typedef struct ug_hip_jpeg_encoder ug_hip_jpeg_encoder;
 int    ug_hip_jpeg_encoder_create(int width, int height, int quality, int restart_interval, ug_hip_jpeg_encoder **out);
-/* subsampling = 420, 422 or 444 (gpujpeg.cpp:406-408 `subsampling=` option); ug_hip_jpeg_encoder_create() is the 420 form. */
+/* subsampling = 420, 422 or 444 (gpujpeg.cpp:406-408 `subsampling=` option); ug_hip_jpeg_encoder_create() is the 420 form.
+ * subsampling = 4444 (GPUJPEG_SUBSAMPLING_4444, what `-c jpeg:alpha` asks of GPUJPEG for RGBA input, gpujpeg.cpp:316-336): R, G, B and alpha,
+ * fed UG_PF_RGBA (bytes R, G, B, A) and nothing else -- the R,G,B 4:4:4 stream of the same options with a fourth component 'A' behind (Adobe
+ * transform 0, every component 1x1 with quantiser and Huffman table 0; interleaved: an MCU of four blocks; UG_JPEG_NONINTERLEAVED: four scans). */
 int    ug_hip_jpeg_encoder_create_sub(int width, int height, int quality, int restart_interval, int subsampling,
                                       ug_hip_jpeg_encoder **out);
 /* The rest of the reference module's encoder options (src/video_compress/gpujpeg.cpp:303-305,396-405):
@@ -449,9 +452,10 @@ int    ug_hip_jpeg_encoder_create_sub(int width, int height, int quality, int re
  *                limited range: RGB input + a Y'CbCr space -> a JFIF-shaped stream, components 1, 2, 3, chroma tables for Cb and Cr (Y601full IS
  *                JFIF); UYVY input + BT.601 (either range) -> the usual 4:2:x stream of the converted samples; UG_JPEG_CS_RGB with RGB input and
  *                UG_JPEG_CS_YCBCR_BT709 with UYVY / I420 input = UG_JPEG_CS_ASIS.  Not offered (UG_HIP_EUNSUPP): R, G, B components with
- *                subsampling 420 / 422, I420 with a conversion (ug_hip_yuv420p_to_uyvy first, as the module does).  The colour stage is UNPINNED towards libgpujpeg like the FDCT: published BT.601 /
+ *                subsampling 420 / 422, I420 with a conversion (ug_hip_yuv420p_to_uyvy first, as the module does), a Y'CbCr space or
+ *                UG_JPEG_INPUT_UYVY with subsampling 4444 (no reader takes Y'CbCr + alpha; UYVY has none).  The colour stage is UNPINNED towards libgpujpeg like the FDCT: published BT.601 /
  *                BT.709 definitions, fp32.
- *   flags        UG_JPEG_NONINTERLEAVED (subsampling 444 only): one scan per component (T.81 A.2.2; restart intervals count blocks of the scan's
+ *   flags        UG_JPEG_NONINTERLEAVED (subsampling 444 / 4444 only): one scan per component (T.81 A.2.2; restart intervals count blocks of the scan's
  *                component) -- the reference's DEFAULT for RGB input (interleaved = 0 unless `:interleaved`, gpujpeg.cpp:303); the header then
  *                carries what those scans use (RGB: quantiser and Huffman table 0 only).  Three coder launches, each going on where the one before
  *                ended (one synchronisation, no intermediate buffer); the single interleaved scan is ONE fused kernel and faster.
@@ -496,13 +500,17 @@ int    ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in
  * JPEG decoder (receive side: gpujpeg_decoder_create / _decode / _destroy behind
  * src/video_decompress/gpujpeg.c:74-140,292-301)
  * ---------------------------------------------------------------------------------- */
-/* Baseline JPEG (8-bit, Huffman; 3 components at 4:4:4 / 4:2:2 / 4:2:0, interleaved or one scan per component; restart intervals make the
+/* Baseline JPEG (8-bit, Huffman; 3 components at 4:4:4 / 4:2:2 / 4:2:0, or 4 at 4:4:4:4, interleaved or one scan per component; restart intervals make the
  * entropy-coded data parallel: one lane per restart segment) -> `out` in device memory:
  *   YCbCr streams -> UG_PF_UYVY (4:2:2: samples as they are; 4:2:0: chroma lines repeated, yuv420p_to_uyvy; 4:4:4: chroma pairs averaged),
  *                    UG_PF_RGB / UG_PF_RGBA (the UYVY form through vc_copylineUYVYtoRGB[A]: BT.709 limited range, as UltraGrid codes it),
  *                    UG_PF_I420 (4:2:0 streams: planes back to back);
  *   R,G,B streams (Adobe APP14 transform 0 or component ids 'R','G','B': what `-c jpeg` writes for RGB input) -> UG_PF_RGB / UG_PF_RGBA
  *                    directly, UG_PF_UYVY through vc_copylineRGBtoUYVY's arithmetic.
+ *   R,G,B,A streams (4 components, each 1x1; no Adobe marker or transform 0: what subsampling 4444 writes, and what libjpeg writes for a 4-channel
+ *                    image) -> as R,G,B streams; UG_PF_RGBA with the shifts (0, 8, 16) carries the A sample in the top byte (GPUJPEG's
+ *                    4444_U8_P0123), other shifts 0xFF there; UG_PF_NONE: plane 3 is A.  Y'CbCr-K (Adobe transform 1 / 2) and subsampled
+ *                    four-component streams: UG_HIP_EUNSUPP.
  *   one-component (greyscale) streams: a Y'CbCr picture with both chroma planes at 128, every output above (what another sender's grey MJPEG needs).
  * The component planes equal libjpeg's bit for bit (integer IDCT jidctint).  `jpeg_host` is host memory (compressed frames arrive from the
  * network); everything after the header parse is asynchronous on `stream` (a stream in pinned memory is read by the copy engine when the stream
@@ -515,7 +523,7 @@ int    ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in
 typedef struct ug_hip_jpeg_decoder ug_hip_jpeg_decoder;
 int  ug_hip_jpeg_decoder_create(ug_hip_jpeg_decoder **out);
 void ug_hip_jpeg_decoder_destroy(ug_hip_jpeg_decoder *dec);
-/* header only: subsampling = 444 / 422 / 420 / 400 (greyscale); any pointer may be NULL */
+/* header only: subsampling = 444 / 422 / 420 / 400 (greyscale) / 4444 (R, G, B, A; is_rgb = 1); any pointer may be NULL */
 int  ug_hip_jpeg_read_info(const void *jpeg_host, size_t len, int *width, int *height, int *subsampling, int *is_rgb, int *restart_interval);
 int  ug_hip_jpeg_decoder_decode(ug_hip_jpeg_decoder *dec, const void *jpeg_host, size_t len, ug_pixfmt_t out, void *dst_dev, int dst_pitch,
                                 int rshift, int gshift, int bshift, ug_hip_stream_t stream);

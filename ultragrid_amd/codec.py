@@ -324,7 +324,7 @@ class JpegEncoder:
         self._out = None
 
     def encode(self, src: torch.Tensor, in_fmt: int = L.PF_UYVY) -> bytes:
-        """src: UYVY (4:2:0 / 4:2:2 encoder), RGB (4:4:4 encoder) or I420 planes back to back (4:2:0 encoder)."""
+        """src: UYVY (4:2:0 / 4:2:2 encoder), RGB (4:4:4 encoder), RGBA (4:4:4:4 encoder, subsampling=4444) or I420 planes back to back (4:2:0 encoder)."""
         import ctypes as C
         src = _u8(src)
         if self._out is None:
@@ -389,12 +389,12 @@ class JpegDecoder:
         return dst
 
     def planes(self, data: bytes):
-        """Decode to the component planes only; returns them cropped to the component sizes (device tensors)."""
+        """Decode to the component planes only; returns them cropped to the component sizes (device tensors): 1, 3 or 4 (R, G, B, A) of them."""
         import ctypes as C
         L.check(L.load().ug_hip_jpeg_decoder_decode(self._h, data, len(data), L.PF_NONE, None, 0, 0, 8, 16, _stream()), "ug_hip_jpeg_decoder_decode")
         torch.cuda.synchronize()
         out = []
-        for c in range(3):
+        for c in range(4):
             p, pitch, w, h = C.c_void_p(), C.c_int(), C.c_int(), C.c_int()
             if L.load().ug_hip_jpeg_decoder_plane(self._h, c, C.byref(p), C.byref(pitch), C.byref(w), C.byref(h)) != 0:
                 break

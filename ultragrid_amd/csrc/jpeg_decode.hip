@@ -70,18 +70,19 @@ void build_dev(const HuffHost &h, HuffDev &d, int lut_bits)
 }
 
 struct Scan {
-        int ns, comp[3], td[3], ta[3];
+        int ns, comp[4], td[4], ta[4];
         size_t data_begin, data_end; // entropy-coded bytes [begin, end) in the stream (end = the marker that follows)
 };
 
 struct Header {
         int width = 0, height = 0, ncomp = 0, ri = 0, adobe = -1;
-        int hs[3] = { 1, 1, 1 }, vs[3] = { 1, 1, 1 }, tq[3] = { 0, 0, 0 }, cid[3] = { 0, 0, 0 };
+        int hs[4] = { 1, 1, 1, 1 }, vs[4] = { 1, 1, 1, 1 }, tq[4] = { 0, 0, 0, 0 }, cid[4] = { 0, 0, 0, 0 };
         int hmax = 1, vmax = 1, mcu_w = 0, mcu_h = 0;
         uint16_t qt[4][64]; // natural order
         HuffHost dc[4], ac[4];
         std::vector<Scan> scans;
-        bool is_rgb() const { return ncomp == 3 && (adobe == 0 || (cid[0] == 'R' && cid[1] == 'G' && cid[2] == 'B')); }
+        // four components: R, G, B, alpha (parse() refuses the Adobe transforms that would make them Y'CbCr-K)
+        bool is_rgb() const { return ncomp == 4 || (ncomp == 3 && (adobe == 0 || (cid[0] == 'R' && cid[1] == 'G' && cid[2] == 'B'))); }
 };
 
 const uint8_t kZigzagHost[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
@@ -133,7 +134,7 @@ int parse(const uint8_t *data, size_t len, Header &h, ParseMode mode)
                         h.height = s[1] << 8 | s[2];
                         h.width = s[3] << 8 | s[4];
                         h.ncomp = s[5];
-                        if ((h.ncomp != 1 && h.ncomp != 3) || seglen < (size_t) 8 + 3 * h.ncomp || !h.width || !h.height) return -1;
+                        if ((h.ncomp != 1 && h.ncomp != 3 && h.ncomp != 4) || seglen < (size_t) 8 + 3 * h.ncomp || !h.width || !h.height) return -1;
                         if (h.width > 16384 || h.height > 16384) return -1; // twice 8K: nothing UltraGrid carries; bounds the work buffers a header can ask for
                         for (int c = 0; c < h.ncomp; c++) {
                                 h.cid[c] = s[6 + 3 * c];
@@ -221,6 +222,9 @@ int parse(const uint8_t *data, size_t len, Header &h, ParseMode mode)
                 pos += 2 + seglen;
         }
         if (!h.width || h.scans.empty()) return -1;
+        if (h.ncomp == 4) { // R, G, B, alpha, each sampled 1x1 (what GPUJPEG's 4:4:4:4 writes); subsampled or Y'CbCr-K (Adobe transform 1, 2) four-component streams are not taken
+                if (h.adobe == 1 || h.adobe == 2 || h.hmax != 1 || h.vmax != 1) return -1;
+        }
         return 0;
 }
 
@@ -364,12 +368,12 @@ __global__ __launch_bounds__(kScanWG) void clean_place_kernel(const uint8_t *__r
 
 // ---- pass 2: Huffman decoding --------------------------------------------------------------------------------------------------------
 struct ScanDev {
-        int ns, comp[3], td[3], ta[3], nbh[3], nbv[3], gw[3]; // blocks per unit and blocks per row of each component's grid
+        int ns, comp[4], td[4], ta[4], nbh[4], nbv[4], gw[4]; // blocks per unit and blocks per row of each component's grid
         int single, bw1, mcu_w, ri;
         int units;
-        int16_t *coef[3];
-        int n_dc, n_ac, dc_tab[3], ac_tab[3]; // the distinct tables of the scan ...
-        int dc_slot[3], ac_slot[3];           // ... and which of them each component uses
+        int16_t *coef[4];
+        int n_dc, n_ac, dc_tab[4], ac_tab[4]; // the distinct tables of the scan ...
+        int dc_slot[4], ac_slot[4];           // ... and which of them each component uses
 };
 
 // The bytes of one segment in the workgroup's LDS copy of the clean stream.  Every symbol: if 32 bits or fewer are left, the window takes
@@ -516,7 +520,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(1, 1))) __launch_bounds__(64) void
                 br.cnt -= l + sz;
                 return sym;
         };
-        int pred[3] = { 0, 0, 0 };
+        int pred[4] = { 0, 0, 0, 0 };
         const int per_seg = sp.ri && sp.ri < sp.units ? sp.ri : sp.units;
         const int u0 = seg * per_seg;
         int16_t *const my = (int16_t *) (tile + lane * kTileWords);
@@ -584,7 +588,7 @@ constexpr int kSyncChunkBits = 1024;
 constexpr int kSyncWG = 256;
 constexpr int kSyncWarm = 16, kSyncOwn = kSyncWG - kSyncWarm; // chunks a workgroup of the settling kernel runs ahead of its own (see there); chunks it owns
 constexpr size_t kSyncMinBytes = 4096;
-constexpr int kSyncMaxUnitBlocks = 12; // blocks of one unit: 3 components of up to 2 x 2 (the layouts the output stage takes have at most 6)
+constexpr int kSyncMaxUnitBlocks = 12; // blocks of one unit: 3 components of up to 2 x 2 (the layouts the output stage takes have at most 6; R,G,B,A 4)
 
 __device__ __forceinline__ unsigned long long sync_pack(uint32_t p, int blk, int z) { return (unsigned long long) p << 16 | (unsigned) blk << 8 | (unsigned) z; }
 
@@ -594,8 +598,8 @@ struct SyncLds {
         LongCodes *longs;
         int blk_k[kSyncMaxUnitBlocks], blk_by[kSyncMaxUnitBlocks], blk_bx[kSyncMaxUnitBlocks]; // the blocks of a unit in scan order: component of the scan, row, column
         int blk_dc[kSyncMaxUnitBlocks], blk_ac[kSyncMaxUnitBlocks];                             // their table slots
-        int nbh[3], nbv[3], gw[3];
-        int16_t *coef[3];
+        int nbh[4], nbv[4], gw[4];
+        int16_t *coef[4];
         int per_unit, row_units, n_dc;
 };
 
@@ -988,11 +992,11 @@ __device__ __forceinline__ void idct_1d(const int (&s)[8], int (&o)[8])
 
 // one lane per block of one component's (MCU-padded) block grid
 struct IdctJob {
-        const int16_t *coef[3]; // zigzag order, as the Huffman kernel leaves them
-        const uint16_t *qt[3];  // 64, natural order
-        uint8_t *plane[3];
-        int gw[3], pitch[3];
-        long n_blocks[3];
+        const int16_t *coef[4]; // zigzag order, as the Huffman kernel leaves them
+        const uint16_t *qt[4];  // 64, natural order
+        uint8_t *plane[4];
+        int gw[4], pitch[4];
+        long n_blocks[4];
 };
 // blockIdx.y = component
 __global__ __launch_bounds__(256) void idct_kernel(IdctJob job)
@@ -1044,15 +1048,17 @@ __global__ __launch_bounds__(256) void idct_kernel(IdctJob job)
         }
 }
 
-// R, G, B planes -> packed RGB / RGBA (shifts as decoder_t has them)
-__global__ void planar_rgb_pack_kernel(const uint8_t *__restrict__ r, const uint8_t *__restrict__ g, const uint8_t *__restrict__ b, int ppitch, uint8_t *__restrict__ dst,
-                                       int dpitch, int width, int height, int rgba, int rs, int gs, int bs)
+// R, G, B planes -> packed RGB / RGBA (shifts as decoder_t has them); a: the alpha plane of an R,G,B,A stream, given only with the shifts
+// (0, 8, 16) -- it goes to the top byte (GPUJPEG's 4444_U8_P0123) -- else the byte the shifts leave is 0xFF
+__global__ void planar_rgb_pack_kernel(const uint8_t *__restrict__ r, const uint8_t *__restrict__ g, const uint8_t *__restrict__ b, const uint8_t *__restrict__ a, int ppitch,
+                                       uint8_t *__restrict__ dst, int dpitch, int width, int height, int rgba, int rs, int gs, int bs)
 {
         const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
         if (x >= width || y >= height) return;
         const uint32_t R = r[(long) y * ppitch + x], G = g[(long) y * ppitch + x], B = b[(long) y * ppitch + x];
         if (rgba) {
-                ((uint32_t *) (dst + (long) y * dpitch))[x] = (0xFFFFFFFFu ^ (0xFFu << rs) ^ (0xFFu << gs) ^ (0xFFu << bs)) | R << rs | G << gs | B << bs;
+                const uint32_t rest = a ? (uint32_t) a[(long) y * ppitch + x] << 24 : 0xFFFFFFFFu ^ (0xFFu << rs) ^ (0xFFu << gs) ^ (0xFFu << bs);
+                ((uint32_t *) (dst + (long) y * dpitch))[x] = rest | R << rs | G << gs | B << bs;
         } else {
                 uint8_t *d = dst + (long) y * dpitch + 3 * x;
                 d[0] = (uint8_t) R, d[1] = (uint8_t) G, d[2] = (uint8_t) B;
@@ -1082,9 +1088,9 @@ struct Decoder {
         size_t scan_cap = 0;
         HuffDev *tabs = nullptr;     // 8 tables
         uint16_t *qt = nullptr;      // 4 x 64
-        int16_t *coef[3] = { nullptr, nullptr, nullptr };
-        uint8_t *plane[3] = { nullptr, nullptr, nullptr };
-        size_t coef_cap[3] = { 0, 0, 0 }, plane_cap[3] = { 0, 0, 0 };
+        int16_t *coef[4] = { nullptr, nullptr, nullptr, nullptr };
+        uint8_t *plane[4] = { nullptr, nullptr, nullptr, nullptr };
+        size_t coef_cap[4] = { 0, 0, 0, 0 }, plane_cap[4] = { 0, 0, 0, 0 };
         uint8_t *tmp = nullptr;      // intermediate packed frame (UYVY or RGB) when the output needs a second conversion
         size_t tmp_cap = 0;
         // scans without restart intervals (pass 2b): per-chunk states and counts, the mapped words the host reads between the launches
@@ -1098,7 +1104,7 @@ struct Decoder {
         uint16_t qt_now[4][64];
         bool tables_valid = false;
         Header hdr;
-        int plane_pitch[3] = { 0, 0, 0 };
+        int plane_pitch[4] = { 0, 0, 0, 0 };
         hipEvent_t uploaded = nullptr; // the pinned staging area may be rewritten once this has happened
         bool upload_pending = false;
 };
@@ -1144,7 +1150,7 @@ void ug_hip_jpeg_decoder_destroy(ug_hip_jpeg_decoder *dec)
         Decoder *d = (Decoder *) dec;
         if (!d) return;
         for (void *p : { (void *) d->stream, (void *) d->clean, (void *) d->seg_start, (void *) d->seg_end, (void *) d->scan_counts, (void *) d->tabs, (void *) d->qt, (void *) d->coef[0], (void *) d->coef[1], (void *) d->coef[2],
-                         (void *) d->plane[0], (void *) d->plane[1], (void *) d->plane[2], (void *) d->tmp, (void *) d->sync_start, (void *) d->sync_exit, (void *) d->sync_wg_last,
+                         (void *) d->coef[3], (void *) d->plane[0], (void *) d->plane[1], (void *) d->plane[2], (void *) d->plane[3], (void *) d->tmp, (void *) d->sync_start, (void *) d->sync_exit, (void *) d->sync_wg_last,
                          (void *) d->sync_nblk, (void *) d->sync_base, (void *) d->sync_chunk_off }) {
                 if (p) (void) hipFree(p);
         }
@@ -1164,7 +1170,7 @@ int ug_hip_jpeg_read_info(const void *jpeg_host, size_t len, int *width, int *he
         }
         if (width) *width = h.width;
         if (height) *height = h.height;
-        if (subsampling) *subsampling = h.ncomp == 1 ? 400 : (h.hs[0] == 2 ? (h.vs[0] == 2 ? 420 : 422) : 444);
+        if (subsampling) *subsampling = h.ncomp == 1 ? 400 : (h.ncomp == 4 ? 4444 : (h.hs[0] == 2 ? (h.vs[0] == 2 ? 420 : 422) : 444));
         if (is_rgb) *is_rgb = h.is_rgb();
         if (restart_interval) *restart_interval = h.ri;
         return UG_HIP_SUCCESS;
@@ -1219,13 +1225,13 @@ int ug_hip_jpeg_decoder_decode_sized(ug_hip_jpeg_decoder *dec, const void *jpeg_
                 ScanDev sp;
                 int n_seg;
         };
-        ScanPlan plan[3];
-        long gw[3], gh[3];
+        ScanPlan plan[4];
+        long gw[4], gh[4];
         for (int c = 0; c < h.ncomp; c++) {
                 gw[c] = (long) h.mcu_w * h.hs[c];
                 gh[c] = (long) h.mcu_h * h.vs[c];
         }
-        if (gw[0] * gh[0] > 0x7FFFFFFF / 64 || h.scans.size() > 3) {
+        if (gw[0] * gh[0] > 0x7FFFFFFF / 64 || h.scans.size() > (h.ncomp == 4 ? 4u : 3u)) {
                 ug::set_last_error_msg("ug_hip_jpeg_decoder_decode: picture too large");
                 return UG_HIP_EUNSUPP;
         }
@@ -1445,15 +1451,17 @@ int ug_hip_jpeg_decoder_decode_sized(ug_hip_jpeg_decoder *dec, const void *jpeg_
                         return UG_HIP_EUNSUPP;
                 }
                 if (out == UG_PF_RGB || out == UG_PF_RGBA) {
+                        // the alpha of an R,G,B,A stream where the shifts leave it the top byte; elsewhere 0xFF (vc_copylineRGBtoRGBA)
+                        const bool alpha = out == UG_PF_RGBA && h.ncomp == 4 && rshift == 0 && gshift == 8 && bshift == 16;
                         hipLaunchKernelGGL(planar_rgb_pack_kernel, dim3((unsigned) ((w + 255) / 256), (unsigned) hh), dim3(256), 0, st, d->plane[0], d->plane[1], d->plane[2],
-                                           d->plane_pitch[0], (uint8_t *) dst_dev, dst_pitch, w, hh, out == UG_PF_RGBA, rshift, gshift, bshift);
+                                           alpha ? d->plane[3] : nullptr, d->plane_pitch[0], (uint8_t *) dst_dev, dst_pitch, w, hh, out == UG_PF_RGBA, rshift, gshift, bshift);
                         UG_HIP_LAUNCH_CHECK();
                         return UG_HIP_SUCCESS;
                 }
                 if (out == UG_PF_UYVY) { // through packed RGB and vc_copylineRGBtoUYVY's arithmetic
                         if (!need_tmp(UG_PF_RGB)) return UG_HIP_ERUNTIME;
                         hipLaunchKernelGGL(planar_rgb_pack_kernel, dim3((unsigned) ((w + 255) / 256), (unsigned) hh), dim3(256), 0, st, d->plane[0], d->plane[1], d->plane[2],
-                                           d->plane_pitch[0], d->tmp, 3 * w, w, hh, 0, 0, 8, 16);
+                                           nullptr, d->plane_pitch[0], d->tmp, 3 * w, w, hh, 0, 0, 8, 16);
                         return ug_hip_pixfmt_convert(UG_PF_RGB, UG_PF_UYVY, d->tmp, dst_dev, w, hh, 0, dst_pitch, 0, 8, 16, stream);
                 }
                 ug::set_last_error_msg("ug_hip_jpeg_decoder_decode: unsupported output codec");

@@ -18,6 +18,13 @@
 #include "ug_common.h"
 #include "jpeg_fdct_device.h"
 
+// jpeg_fdct.hip: packed RGBA (4 B/px) -> R, G, B and A blocks (4:4:4:4), all with the divisors `div` -- declared here, its one caller, rather than in
+// ug_common.h, whose hash names the build that profiles/pmc_traffic.json's counters were taken on
+namespace ug {
+int jpeg_fdct_quant_rgba4444(const void *src, int pitch, int width, int height, int blocks_w, int blocks_h, const float *div,
+                             int16_t *out_r, int16_t *out_g, int16_t *out_b, int16_t *out_a, ug_hip_stream_t stream);
+}
+
 namespace {
 
 #include "jpeg_huffman_tables.h"
@@ -78,9 +85,9 @@ struct BatchStride {
 constexpr int kMaxBatch = 16; // frames per encode_batch call (the pinned length words of an encoder)
 
 __global__ __launch_bounds__(256) void entropy_wave_kernel(const int16_t *__restrict__ cy, const int16_t *__restrict__ cb,
-                                                           const int16_t *__restrict__ cr, int mcu_w, int n_mcu, int hs, int vs /* sampling factors of component 0: 2x2 (4:2:0), 2x1 (4:2:2), 1x1 (4:4:4) */,
+                                                           const int16_t *__restrict__ cr, const int16_t *__restrict__ ca /* nc = 3: the alpha plane */, int mcu_w, int n_mcu, int hs, int vs /* sampling factors of component 0: 2x2 (4:2:0), 2x1 (4:2:2), 1x1 (4:4:4) */,
                                                            int ctab /* Huffman table set of components 1,2: 1 = chroma (YCbCr), 0 = same as component 0 (RGB) */,
-                                                           int nc /* components behind component 0 in the MCU: 2, or 0 for one scan of a non-interleaved stream (cy = that component) */,
+                                                           int nc /* components behind component 0 in the MCU: 2 (3: R, G, B, A), or 0 for one scan of a non-interleaved stream (cy = that component) */,
                                                            int tab0 /* Huffman table set of component 0 */, int ri, int n_seg,
                                                            uint32_t *__restrict__ raw, int cap_words, uint32_t *__restrict__ seg_len,
                                                            uint32_t *__restrict__ seg_ff /* final size of the segment */,
@@ -88,7 +95,7 @@ __global__ __launch_bounds__(256) void entropy_wave_kernel(const int16_t *__rest
 {
         __shared__ uint32_t ac_tab[2][256], dc_tab[2][12];
         __shared__ uint32_t win[4][68];
-        cy += blockIdx.y * bs.coef_y; cb += blockIdx.y * bs.coef_c; cr += blockIdx.y * bs.coef_c;
+        cy += blockIdx.y * bs.coef_y; cb += blockIdx.y * bs.coef_c; cr += blockIdx.y * bs.coef_c; ca += blockIdx.y * bs.coef_c;
         raw += blockIdx.y * bs.raw_words; seg_len += blockIdx.y * bs.seg; seg_ff += blockIdx.y * bs.seg; chunk_tot += blockIdx.y * bs.tot_words;
         for (int i = threadIdx.x; i < 512; i += 256) ac_tab[i >> 8][i & 255] = kAcTab[i >> 8][i & 255];
         if (threadIdx.x < 24) dc_tab[threadIdx.x / 12][threadIdx.x % 12] = kDcTab[threadIdx.x / 12][threadIdx.x % 12];
@@ -100,7 +107,7 @@ __global__ __launch_bounds__(256) void entropy_wave_kernel(const int16_t *__rest
         uint32_t *out = raw + (size_t) seg * cap_words;
         uint32_t carry_word = 0; // partial word, bits left-aligned
         int carry_bits = 0, wbase = 0, ff = 0;
-        int pred[3] = { 0, 0, 0 };
+        int pred[4] = { 0, 0, 0, 0 };
         const int ybl = hs * vs, per_mcu = ybl + nc;
         const int m0 = seg * ri, n_blk = per_mcu * (min(n_mcu, (seg + 1) * ri) - m0);
         // Walk the blocks of the segment in scan order (per MCU: Y00 Y01 [Y10 Y11] Cb Cr) with incrementally updated
@@ -110,7 +117,7 @@ __global__ __launch_bounds__(256) void entropy_wave_kernel(const int16_t *__rest
         auto next_ptr = [&]() { // pointer of block (m, b_next), then advance
                 const int yrow = vs * my + (hs == 2 ? b_next >> 1 : 0), ycol = hs * mx + (hs == 2 ? b_next & 1 : 0); // block of component 0
                 const int16_t *p = b_next < ybl ? cy + 64 * ((long) yrow * (hs * mcu_w) + ycol)
-                                                : (b_next == ybl ? cb : cr) + 64L * m;
+                                                : (b_next == ybl ? cb : (b_next == ybl + 1 ? cr : ca)) + 64L * m;
                 if (++b_next == per_mcu) {
                         b_next = 0;
                         m++;
@@ -553,7 +560,7 @@ __device__ __forceinline__ uint32_t lookback_exclusive_flat(unsigned long long *
 struct CodeArgs {
         // scan geometry
         int mcu_w, n_mcu, hs, vs, ctab, ri, n_seg, S /* blocks per full segment */, G /* segments per workgroup (SRC = 0) */, n_wg /* workgroups per frame */;
-        // SRC = 0 only: nc = chroma blocks of an MCU -- 2, or 0 for the scan of ONE component (a non-interleaved scan, T.81 A.2.2: its MCU is one block, cy = that
+        // SRC = 0 only: nc = chroma blocks of an MCU -- 2 (3: R, G, B, A, the fourth plane in ca), or 0 for the scan of ONE component (a non-interleaved scan, T.81 A.2.2: its MCU is one block, cy = that
         // component's blocks); tab0 = the Huffman table pair of the blocks b < hs * vs (0; 1 for the Cb / Cr scans of a non-interleaved YCbCr stream)
         int nc, tab0;
         // SRC = 0, one-launch placement only: the stream of frame f goes on at byte base[f] - 2 of its buffer -- behind the previous scan of a non-interleaved stream,
@@ -561,7 +568,7 @@ struct CodeArgs {
         // stream run in order, so it is final when this launch reads it.
         const uint32_t *base;
         // SRC = 0: quantised blocks in HBM, per-frame strides in int16 elements
-        const int16_t *cy, *cb, *cr;
+        const int16_t *cy, *cb, *cr, *ca;
         long coef_y, coef_c;
         // SRC = 420 / 422: the UYVY frame(s) and the quantiser (luma 64 divisors, chroma 64)
         const uint8_t *src;
@@ -706,11 +713,12 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SRC 
         if (SRC == 0) {
                 identify();
                 init_tables();
-                const int16_t *const cy = a.cy + frame * a.coef_y, *const cb = a.cb + frame * a.coef_c, *const cr = a.cr + frame * a.coef_c;
+                const int16_t *const cy = a.cy + frame * a.coef_y, *const cb = a.cb + frame * a.coef_c, *const cr = a.cr + frame * a.coef_c,
+                              *const ca = a.ca + frame * a.coef_c;
                 const int m = m_first + ml;
                 const int my = m / a.mcu_w, mx = m - my * a.mcu_w;
                 const int yrow = a.vs * my + (a.hs == 2 ? b >> 1 : 0), ycol = a.hs * mx + (a.hs == 2 ? b & 1 : 0);
-                const int16_t *p = b < ybl ? cy + 64 * ((long) yrow * (a.hs * a.mcu_w) + ycol) : (b == ybl ? cb : cr) + 64L * m;
+                const int16_t *p = b < ybl ? cy + 64 * ((long) yrow * (a.hs * a.mcu_w) + ycol) : (b == ybl ? cb : (b == ybl + 1 ? cr : ca)) + 64L * m;
                 if (!active) p = cy;
                 // A block is one 128-byte line.  If every lane fetched its own block 16 bytes at a time, each of the 8 load
                 // instructions of the wave would touch 64 different lines and use an eighth of each: 8x the traffic between L2 and
@@ -1064,9 +1072,11 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SRC 
                 }
                 __syncthreads();
         };
-        const uint32_t base0 = SRC == 0 && a.base != nullptr ? a.base[frame] - 2u : 0u; // (wave-uniform: a scalar load)
+        // (a base below 2 -- no length left by the previous scan -- leaves no room at all: nothing of this scan is written)
+        const uint32_t base_in = SRC == 0 && a.base != nullptr ? a.base[frame] : 2u; // (wave-uniform: a scalar load)
+        const uint32_t base0 = base_in >= 2u ? base_in - 2u : 0u;
         uint8_t *const out = a.slots != nullptr ? a.slots + ((size_t) frame * a.n_wg + wg) * a.slot_bytes : a.out + (size_t) frame * a.out_stride + base0;
-        const size_t capacity = a.slots != nullptr ? a.slot_bytes : (a.capacity > base0 ? a.capacity - base0 : 0);
+        const size_t capacity = a.slots != nullptr ? a.slot_bytes : (base_in >= 2u && a.capacity > base0 ? a.capacity - base0 : 0);
         // the window words of this pass to their place in the stream, 0x00 after every 0xFF; after the last pass RSTm / EOI
         auto write_pass = [&](int lo_idx, bool last_pass, bool pad) {
 #pragma unroll 1
@@ -1113,7 +1123,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SRC 
                         }
                 }
         };
-        if (wg == 0 && a.slots == nullptr) { // the first workgroup also lays down SOI .. SOS
+        if (wg == 0 && a.slots == nullptr && (size_t) a.header_len <= capacity) { // the first workgroup also lays down SOI .. SOS (a later scan: its SOS), where it fits
                 for (int i = tid; i < a.header_len; i += W) out[i] = a.header[i];
         }
         UG_PHASE(3) // positions (two barriers: the other waves' walks end here)
@@ -1312,9 +1322,10 @@ __global__ __launch_bounds__(256) void compact_kernel(const uint8_t *__restrict_
 {
         raw += blockIdx.y * bs.raw_words * 4; seg_len += blockIdx.y * bs.seg; seg_ff += blockIdx.y * bs.seg;
         chunk_tot += blockIdx.y * bs.tot_words; out += blockIdx.y * bs.out_bytes; total_pinned += blockIdx.y;
-        const uint32_t base0 = base != nullptr ? base[blockIdx.y] - 2u : 0u; // a later scan of a non-interleaved stream goes on over the EOI of the one before
+        const uint32_t base_in = base != nullptr ? base[blockIdx.y] : 2u; // a later scan of a non-interleaved stream goes on over the EOI of the one before
+        const uint32_t base0 = base_in >= 2u ? base_in - 2u : 0u;
         out += base0;
-        capacity = capacity > base0 ? capacity - base0 : 0;
+        capacity = base_in >= 2u && capacity > base0 ? capacity - base0 : 0;
         if (blockIdx.x == 0 && (size_t) header_len <= capacity) { // the first workgroup also lays down SOI .. SOS (a later scan: its SOS)
                 for (int i = threadIdx.x; i < header_len; i += 256) out[i] = header[i];
         }
@@ -1357,7 +1368,7 @@ __global__ __launch_bounds__(256) void compact_kernel(const uint8_t *__restrict_
 // of a zeroed buffer (atomic OR: blocks share words at their ends), and byte stuffing is one more count / prefix sum / move over 64-byte pieces of the buffer.  The
 // stream is the sequential coder's, bit for bit (tests/test_jpeg_colour_options.py::test_gpu_no_restart_intervals).
 struct NoriScan {
-        const int16_t *c0, *c1, *c2; // component 0 (hs x vs blocks per MCU), the components behind it (nc = 2) -- or one component alone (nc = 0: a scan of a non-interleaved stream)
+        const int16_t *c0, *c1, *c2, *c3; // component 0 (hs x vs blocks per MCU), the components behind it (nc = 2; 3: R, G, B, A) -- or one component alone (nc = 0: a scan of a non-interleaved stream)
         int mcu_w, n_mcu, hs, vs, nc, tab0, ctab;
         int ri; // MCUs per restart interval (the predictions start from 0 there); n_mcu: none
 };
@@ -1377,7 +1388,7 @@ __device__ __forceinline__ const int16_t *nori_block(const NoriScan &s, uint32_t
                 pred = j > 0 ? luma(m, j - 1)[0] : (m % s.ri ? luma(m - 1, ybl - 1)[0] : 0);
                 return luma(m, j);
         }
-        const int16_t *const plane = j == ybl ? s.c1 : s.c2;
+        const int16_t *const plane = j == ybl ? s.c1 : (j == ybl + 1 ? s.c2 : s.c3);
         tab = s.ctab;
         pred = m % s.ri ? plane[64L * (m - 1)] : 0;
         return plane + 64L * m;
@@ -1592,9 +1603,10 @@ __global__ __launch_bounds__(256) void nori_place_kernel(const uint32_t *__restr
                                                          uint8_t *__restrict__ out, const uint8_t *__restrict__ header, int header_len, size_t capacity, uint32_t *__restrict__ total_pinned,
                                                          const uint32_t *__restrict__ base, int frame)
 {
-        const uint32_t base0 = base != nullptr ? base[frame] - 2u : 0u;
+        const uint32_t base_in = base != nullptr ? base[frame] : 2u;
+        const uint32_t base0 = base_in >= 2u ? base_in - 2u : 0u;
         out += base0;
-        capacity = capacity > base0 ? capacity - base0 : 0;
+        capacity = base_in >= 2u && capacity > base0 ? capacity - base0 : 0;
         const uint32_t bytes = (*total_bits + 7) / 8;
         const uint32_t total = (uint32_t) header_len + bytes + ff_before[n_pieces] + 2u;
         if (blockIdx.x == 0 && (size_t) header_len <= capacity) {
@@ -1627,6 +1639,7 @@ struct Encoder {
         // device workspace
         float *div;
         int16_t *cy, *cb, *cr;
+        int16_t *ca;       // the alpha plane of a 4:4:4:4 encoder (NULL otherwise)
         uint32_t *scratch; // per-segment scan data before byte stuffing, cap bytes each
         uint32_t *seg_len, *seg_ff;
         uint32_t *chunk_tot;    // sums of seg_ff per kChunk segments (cleared before every call's coder)
@@ -1656,10 +1669,14 @@ struct Encoder {
         int cs_444;
         uint8_t *cs_tmp;       // the converted frame(s)
         size_t cs_tmp_bytes;
-        std::vector<uint8_t> scan_header[3]; // non-interleaved: what precedes the entropy-coded bytes of scan c (scan 0: the whole header)
-        uint8_t *scan_header_dev[3];
+        bool alpha;    // subsampling 4444: R, G, B and alpha (GPUJPEG_SUBSAMPLING_4444, gpujpeg.cpp:316-336), RGBA input, a fourth 1x1 component
+        int nc;        // components behind component 0 in an MCU: 2, or 3 with alpha
+        std::vector<uint8_t> scan_header[4]; // non-interleaved: what precedes the entropy-coded bytes of scan c (scan 0: the whole header)
+        uint8_t *scan_header_dev[4];
 };
 constexpr int kTotalWords = 32; // per block of total_host: kMaxBatch lengths, [kMaxBatch] "a wait was given up", [kMaxBatch + 1] "a slot overflowed"
+// total_host: the call's block, one per scan of a non-interleaved stream (up to four), one for odd words
+constexpr int kTotalBlocks = 6, kOddBlock = kTotalBlocks - 1;
 
 void put16(std::vector<uint8_t> &v, int x) { v.push_back((uint8_t) (x >> 8)); v.push_back((uint8_t) x); }
 
@@ -1668,11 +1685,12 @@ void put16(std::vector<uint8_t> &v, int x) { v.push_back((uint8_t) (x >> 8)); v.
 // GPUJPEG_RGB, gpujpeg.cpp:303-305), signalled the libjpeg way: Adobe APP14 with transform 0 and ids 'R','G','B'; every component uses
 // quantiser / Huffman table 0.  4:4:4, ycc: JFIF again, components 1, 2, 3 at 1x1.  scan >= 0: the header of a NON-INTERLEAVED stream up to and
 // including the SOS of its first scan (scan = 0; an R, G, B stream then carries table 0 only, the layout of tests/jpeg_bitstream.py
-// write_jpeg_noninterleaved), or just the SOS segment of scan 1 / 2.
-std::vector<uint8_t> build_header(int w, int h, const uint8_t *ql, const uint8_t *qc, int ri, int sub, bool ycc = false, int scan = -1)
+// write_jpeg_noninterleaved), or just the SOS segment of scan 1 / 2 (/ 3).  alpha: the R, G, B stream with a fourth component 'A' behind them, sampled
+// 1x1, tables 0 like the others (4:4:4:4).
+std::vector<uint8_t> build_header(int w, int h, const uint8_t *ql, const uint8_t *qc, int ri, int sub, bool ycc = false, int scan = -1, bool alpha = false)
 {
         const bool rgb = sub == 444 && !ycc;
-        const uint8_t id[3] = { (uint8_t) (rgb ? 'R' : 1), (uint8_t) (rgb ? 'G' : 2), (uint8_t) (rgb ? 'B' : 3) };
+        const uint8_t id[4] = { (uint8_t) (rgb ? 'R' : 1), (uint8_t) (rgb ? 'G' : 2), (uint8_t) (rgb ? 'B' : 3), 'A' };
         const uint8_t t12 = rgb ? 0 : 1;
         std::vector<uint8_t> v;
         if (scan > 0) {
@@ -1690,10 +1708,11 @@ std::vector<uint8_t> build_header(int w, int h, const uint8_t *ql, const uint8_t
                 v.insert(v.end(), { 0xFF, 0xDB, 0, 67, (uint8_t) t });
                 for (int i = 0; i < 64; i++) v.push_back((t ? qc : ql)[kZigHost[i]]);
         }
-        v.insert(v.end(), { 0xFF, 0xC0, 0, 17, 8 });
+        v.insert(v.end(), { 0xFF, 0xC0, 0, (uint8_t) (alpha ? 20 : 17), 8 });
         put16(v, h); put16(v, w);
         const uint8_t s0 = sub == 420 ? 0x22 : (sub == 422 ? 0x21 : 0x11); // H x V sampling of component 0
-        v.insert(v.end(), { 3, id[0], s0, 0, id[1], 0x11, t12, id[2], 0x11, t12 });
+        v.insert(v.end(), { (uint8_t) (alpha ? 4 : 3), id[0], s0, 0, id[1], 0x11, t12, id[2], 0x11, t12 });
+        if (alpha) v.insert(v.end(), { id[3], 0x11, 0 });
         const struct { int tc, th; const uint8_t *bits, *vals; int n; } dht[4] = {
                 { 0, 0, kDcL_bits, kDcL_vals, (int) sizeof kDcL_vals }, { 1, 0, kAcL_bits, kAcL_vals, (int) sizeof kAcL_vals },
                 { 0, 1, kDcC_bits, kDcC_vals, (int) sizeof kDcC_vals }, { 1, 1, kAcC_bits, kAcC_vals, (int) sizeof kAcC_vals } };
@@ -1711,6 +1730,8 @@ std::vector<uint8_t> build_header(int w, int h, const uint8_t *ql, const uint8_t
         }
         if (scan == 0) {
                 v.insert(v.end(), { 0xFF, 0xDA, 0, 8, 1, id[0], 0x00, 0, 63, 0 });
+        } else if (alpha) {
+                v.insert(v.end(), { 0xFF, 0xDA, 0, 14, 4, id[0], 0x00, id[1], 0x00, id[2], 0x00, id[3], 0x00, 0, 63, 0 });
         } else {
                 const uint8_t h12 = (uint8_t) (t12 * 0x11);
                 v.insert(v.end(), { 0xFF, 0xDA, 0, 12, 3, id[0], 0x00, id[1], h12, id[2], h12, 0, 63, 0 });
@@ -1741,7 +1762,7 @@ void free_raw(Encoder *e)
 
 void free_workspace(Encoder *e)
 {
-        for (void **p : { (void **) &e->cy, (void **) &e->cb, (void **) &e->cr, (void **) &e->status, (void **) &e->slots, (void **) &e->wg_bytes }) {
+        for (void **p : { (void **) &e->cy, (void **) &e->cb, (void **) &e->cr, (void **) &e->ca, (void **) &e->status, (void **) &e->slots, (void **) &e->wg_bytes }) {
                 if (*p) (void) hipFree(*p);
                 *p = nullptr;
         }
@@ -1760,6 +1781,7 @@ hipError_t alloc_workspace(Encoder *e, int frames)
         alloc((void **) &e->cy, (size_t) bs.coef_y * 2);
         alloc((void **) &e->cb, (size_t) bs.coef_c * 2);
         alloc((void **) &e->cr, (size_t) bs.coef_c * 2);
+        if (e->alpha) alloc((void **) &e->ca, (size_t) bs.coef_c * 2);
         alloc((void **) &e->status, (size_t) e->n_mcu * 8);
         alloc((void **) &e->wg_bytes, (size_t) e->n_mcu * 4);
         e->slots = nullptr; // (grown on first use)
@@ -1804,7 +1826,7 @@ void destroy(Encoder *e)
                 }
         }
         for (void *p : { (void *) e->div, (void *) e->header_dev, (void *) e->ticket, (void *) e->prof, (void *) e->cs_tmp,
-                         (void *) e->scan_header_dev[0], (void *) e->scan_header_dev[1], (void *) e->scan_header_dev[2] }) {
+                         (void *) e->scan_header_dev[0], (void *) e->scan_header_dev[1], (void *) e->scan_header_dev[2], (void *) e->scan_header_dev[3] }) {
                 if (p) (void) hipFree(p);
         }
         if (e->total_host) (void) hipHostFree(e->total_host);
@@ -1823,20 +1845,29 @@ int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restar
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create: bad arguments");
                 return UG_HIP_EINVAL;
         }
-        if (subsampling != 420 && subsampling != 422 && subsampling != 444) {
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_create: subsampling must be 420, 422 or 444");
+        if (subsampling != 420 && subsampling != 422 && subsampling != 444 && subsampling != 4444) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_create: subsampling must be 420, 422, 444 or 4444");
                 return UG_HIP_EUNSUPP;
         }
         if (internal_cs < UG_JPEG_CS_ASIS || internal_cs > UG_JPEG_CS_YCBCR_BT709 || (flags & ~(UG_JPEG_NONINTERLEAVED | UG_JPEG_INPUT_UYVY))) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create_ex: unknown colour space or flag");
                 return UG_HIP_EINVAL;
         }
+        // 4:4:4:4 = R, G, B + alpha from RGBA input: no reader takes Y'CbCr + alpha, and UYVY carries no alpha
+        const bool alpha = subsampling == 4444;
+        if (alpha && ((internal_cs != UG_JPEG_CS_ASIS && internal_cs != UG_JPEG_CS_RGB) || (flags & UG_JPEG_INPUT_UYVY))) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_create_ex: a 4:4:4:4 stream is R, G, B, alpha from RGBA input");
+                return UG_HIP_EUNSUPP;
+        }
+        if (alpha) subsampling = 444; // the R, G, B stream of the same options, a fourth component behind
         if (subsampling != 444 && ((flags & (UG_JPEG_NONINTERLEAVED | UG_JPEG_INPUT_UYVY)) || internal_cs == UG_JPEG_CS_RGB)) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create_ex: a 4:2:x stream is Y'CbCr in one interleaved scan (R, G, B components, one scan per component, "
                                        "UG_JPEG_INPUT_UYVY: 4:4:4)");
                 return UG_HIP_EUNSUPP;
         }
         Encoder *e = new Encoder();
+        e->alpha = alpha;
+        e->nc = alpha ? 3 : 2;
         e->nonint = (flags & UG_JPEG_NONINTERLEAVED) != 0;
         e->in_uyvy = (flags & UG_JPEG_INPUT_UYVY) != 0;
         e->cs_444 = internal_cs;
@@ -1858,22 +1889,22 @@ int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restar
         // header -- coded by a single wave, block after block (entropy_wave_kernel): milliseconds per frame instead of microseconds; for streams a reader without
         // restart marker support must take
         e->ri = restart_interval ? restart_interval : e->n_mcu;
-        if ((long) e->ri * (e->ybl + 2) * kRawBytesPerBlock + 8 > (1L << 30)) {
+        if ((long) e->ri * (e->ybl + e->nc) * kRawBytesPerBlock + 8 > (1L << 30)) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create: picture too large for a scan without restart intervals");
                 delete e;
                 return UG_HIP_EUNSUPP;
         }
         e->n_seg = (e->n_mcu + e->ri - 1) / e->ri;
-        e->cap = e->ri * (e->ybl + 2) * kRawBytesPerBlock + 8; // unstuffed scan bytes of one segment (worst case 27 bits per coefficient)
+        e->cap = e->ri * (e->ybl + e->nc) * kRawBytesPerBlock + 8; // unstuffed scan bytes of one segment (worst case 27 bits per coefficient)
         uint8_t ql[64], qc[64];
         float div[128];
         ug_hip_jpeg_qtable(quality, 0, ql);
         ug_hip_jpeg_qtable(quality, 1, qc);
         ug_hip_jpeg_divisors(ql, div);
         ug_hip_jpeg_divisors(e->ctab == 0 ? ql : qc, div + 64); // R, G, B: every component is quantised with table 0
-        e->header = build_header(width, height, ql, qc, restart_interval, e->sub, e->ycc);
+        e->header = build_header(width, height, ql, qc, restart_interval, e->sub, e->ycc, -1, e->alpha);
         if (e->nonint) {
-                for (int c = 0; c < 3; c++) e->scan_header[c] = build_header(width, height, ql, qc, restart_interval, e->sub, e->ycc, c);
+                for (int c = 0; c < 1 + e->nc; c++) e->scan_header[c] = build_header(width, height, ql, qc, restart_interval, e->sub, e->ycc, c, e->alpha);
                 e->header = e->scan_header[0]; // (what max_size and the capacity check count)
         }
         hipError_t err = hipSuccess;
@@ -1890,9 +1921,9 @@ int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restar
         }
         static_assert(kMaxBatch * sizeof(uint32_t) <= 64, "one length word per frame of a batch");
         static_assert(kMaxBatch + 2 <= kTotalWords, "lengths + the two flag words");
-        if (err == hipSuccess) err = hipHostMalloc((void **) &e->total_host, 5 * kTotalWords * 4, hipHostMallocMapped); // the call's block, one per scan, one for odd words
-        if (err == hipSuccess) memset(e->total_host, 0, 5 * kTotalWords * 4);
-        for (int c = 0; c < 3 && e->nonint; c++) {
+        if (err == hipSuccess) err = hipHostMalloc((void **) &e->total_host, kTotalBlocks * kTotalWords * 4, hipHostMallocMapped);
+        if (err == hipSuccess) memset(e->total_host, 0, kTotalBlocks * kTotalWords * 4);
+        for (int c = 0; c < 1 + e->nc && e->nonint; c++) {
                 alloc((void **) &e->scan_header_dev[c], e->scan_header[c].size());
                 if (err == hipSuccess) err = hipMemcpy(e->scan_header_dev[c], e->scan_header[c].data(), e->scan_header[c].size(), hipMemcpyHostToDevice);
         }
@@ -1923,7 +1954,8 @@ void ug_hip_jpeg_encoder_destroy(ug_hip_jpeg_encoder *enc) { destroy((Encoder *)
 size_t ug_hip_jpeg_encoder_max_size(const ug_hip_jpeg_encoder *enc)
 {
         const Encoder *e = (const Encoder *) enc;
-        return e ? e->header.size() + 20 + (size_t) e->n_seg * (2 * (size_t) e->cap + 2) : 0; // every byte stuffed = worst case (+ the SOS of two more scans)
+        // every byte stuffed = worst case (+ the SOS of two more scans; three with alpha)
+        return e ? e->header.size() + (e->alpha ? 30 : 20) + (size_t) e->n_seg * (2 * (size_t) e->cap + 2) : 0;
 }
 
 int ug_hip_jpeg_encoder_encode(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, const void *src_dev, int src_pitch, void *out_dev,
@@ -1958,7 +1990,7 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
         bs.out_bytes = (long) out_stride;
         int rc = UG_HIP_SUCCESS;
         const int w = e->width, h = e->height;
-        const int S_frame = e->ri * (e->ybl + 2); // blocks per (full) restart segment
+        const int S_frame = e->ri * (e->ybl + e->nc); // blocks per (full) restart segment
         const bool wave_path = (e->nonint ? e->ri : S_frame) > 256 || e->force_wave_kernel; // (a scan of one component: a segment is ri blocks)
         if (!src_pitch && in == UG_PF_UYVY) src_pitch = ug::linesize(UG_PF_UYVY, w);
         // ---- the colour stage (create_ex's internal_cs): the frame(s) converted into a buffer of the encoder's, which then takes the input's place ----
@@ -1985,8 +2017,12 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 src_pitch = ls;
                 src_stride = fb;
         }
+        if (e->alpha != (in == UG_PF_RGBA)) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:4:4:4 encoder takes RGBA, and only it takes RGBA");
+                return UG_HIP_EUNSUPP;
+        }
         // ---- a 4:4:4 encoder fed UYVY (UG_JPEG_INPUT_UYVY): the frame(s) as 3 B/px in the coded colour space, which then take the place of RGB input ----
-        if (e->sub == 444 && e->in_uyvy != (in == UG_PF_UYVY)) {
+        if (e->sub == 444 && !e->alpha && e->in_uyvy != (in == UG_PF_UYVY)) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:4:4 encoder takes RGB, or UYVY when created with UG_JPEG_INPUT_UYVY");
                 return UG_HIP_EUNSUPP;
         }
@@ -2038,6 +2074,13 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                                 rc = ug::jpeg_fdct_quant_rgb444(fr, src_pitch, w, h, e->mcu_w, e->mcu_h, e->div, e->cy + f * bs.coef_y, e->cb + f * bs.coef_c, e->cr + f * bs.coef_c, stream);
                         }
                 }
+        } else if (in == UG_PF_RGBA && e->alpha) { // GPUJPEG_4444_U8_P0123: R, G, B, A in one pass over the frame (rgba_jpeg4444_kernel)
+                if (!src_pitch) src_pitch = 4 * w;
+                for (int f = 0; f < frames && rc == UG_HIP_SUCCESS; f++) {
+                        const uint8_t *const fr = (const uint8_t *) src_dev + f * src_stride;
+                        rc = ug::jpeg_fdct_quant_rgba4444(fr, src_pitch, w, h, e->mcu_w, e->mcu_h, e->div, e->cy + f * bs.coef_y, e->cb + f * bs.coef_c, e->cr + f * bs.coef_c,
+                                                          e->ca + f * bs.coef_c, stream);
+                }
         } else if (in == UG_PF_I420 && e->sub == 420) { // planar passthrough (GPUJPEG_420_U8_P0P1P2, gpujpeg.cpp:335): Y, U, V planes back to back
                 if (src_pitch && src_pitch != w) {
                         ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: I420 input must be tightly packed");
@@ -2051,7 +2094,7 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                         if (rc == UG_HIP_SUCCESS) rc = ug::jpeg_fdct_quant_strided(v, cw, 1, cw, ch, e->mcu_w, e->mcu_h, e->div + 64, e->cr + f * bs.coef_c, nullptr, stream);
                 }
         } else {
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: input must be UYVY (4:2:0 / 4:2:2 encoder), I420 (4:2:0) or RGB (4:4:4); "
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: input must be UYVY (4:2:0 / 4:2:2 encoder), I420 (4:2:0), RGB (4:4:4) or RGBA (4:4:4:4); "
                                        "convert other formats with ug_hip_pixfmt_convert");
                 return UG_HIP_EUNSUPP;
         }
@@ -2070,8 +2113,8 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 }
                 CodeArgs a = {};
                 a.mcu_w = e->mcu_w; a.n_mcu = e->n_mcu; a.hs = e->hs; a.vs = e->vs; a.ctab = e->ctab; a.ri = e->ri; a.n_seg = e->n_seg; a.S = S;
-                a.nc = scan ? 0 : 2; a.tab0 = scan ? scan->tab0 : 0;
-                a.cy = scan ? scan->coef : e->cy; a.cb = e->cb; a.cr = e->cr; a.coef_y = bs.coef_y; a.coef_c = bs.coef_c;
+                a.nc = scan ? 0 : e->nc; a.tab0 = scan ? scan->tab0 : 0;
+                a.cy = scan ? scan->coef : e->cy; a.cb = e->cb; a.cr = e->cr; a.ca = e->ca; a.coef_y = bs.coef_y; a.coef_c = bs.coef_c;
                 a.src = (const uint8_t *) src_dev; a.pitch = src_pitch; a.width = w; a.height = h; a.src_stride = src_stride;
                 a.out = (uint8_t *) out_dev; a.out_stride = out_stride; a.capacity = out_capacity; a.header = e->header_dev; a.header_len = (int) e->header.size();
                 a.total_pinned = e->total_host_dev;
@@ -2167,15 +2210,16 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
         static const bool nori_off = getenv("UG_JPEG_NORI") != nullptr && getenv("UG_JPEG_NORI")[0] == '0';
         const bool nori = wave_path && !e->force_wave_kernel && e->n_seg == 1 && !nori_off && (unsigned long long) e->cap * 8ull < (1ull << 32); // (UG_JPEG_WAVE_KERNEL=1: the old kernels throughout)
         auto code_without_restart = [&](const ScanPlan *scan) -> int {
-                const uint32_t n_blocks = (uint32_t) e->n_mcu * (uint32_t) (scan ? 1 : e->ybl + 2);
-                if (!e->nori_bits) UG_HIP_TRY(hipMalloc((void **) &e->nori_bits, ((size_t) e->n_mcu * (e->ybl + 2) + 1) * 4));
+                const uint32_t n_blocks = (uint32_t) e->n_mcu * (uint32_t) (scan ? 1 : e->ybl + e->nc);
+                if (!e->nori_bits) UG_HIP_TRY(hipMalloc((void **) &e->nori_bits, ((size_t) e->n_mcu * (e->ybl + e->nc) + 1) * 4));
                 for (int f = 0; f < frames; f++) {
                         NoriScan s = {};
                         s.c0 = (scan ? scan->coef : e->cy) + f * bs.coef_y; s.c1 = e->cb + f * bs.coef_c; s.c2 = e->cr + f * bs.coef_c;
-                        s.mcu_w = e->mcu_w; s.n_mcu = e->n_mcu; s.hs = scan ? 1 : e->hs; s.vs = scan ? 1 : e->vs; s.nc = scan ? 0 : 2; s.tab0 = scan ? scan->tab0 : 0; s.ctab = e->ctab; s.ri = e->n_mcu;
+                        s.c3 = e->ca ? e->ca + f * bs.coef_c : nullptr;
+                        s.mcu_w = e->mcu_w; s.n_mcu = e->n_mcu; s.hs = scan ? 1 : e->hs; s.vs = scan ? 1 : e->vs; s.nc = scan ? 0 : e->nc; s.tab0 = scan ? scan->tab0 : 0; s.ctab = e->ctab; s.ri = e->n_mcu;
                         hipLaunchKernelGGL(nori_len_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, e->nori_bits);
                         hipLaunchKernelGGL(nori_scan_kernel, dim3(1), dim3(1024), 0, st, e->nori_bits, n_blocks);
-                        uint32_t *const bits_host = e->total_host + 4 * kTotalWords; // (a word of the pinned block of its own)
+                        uint32_t *const bits_host = e->total_host + kOddBlock * kTotalWords; // (a word of the pinned block of its own)
                         UG_HIP_TRY(hipMemcpyAsync(bits_host, e->nori_bits + n_blocks, 4, hipMemcpyDeviceToHost, st));
                         UG_HIP_TRY(hipStreamSynchronize(st));
                         const size_t bytes = ((size_t) *bits_host + 7) / 8;
@@ -2203,10 +2247,10 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
         // (which is faster, profiles/r06_encode_no_restart.txt: the old kernel takes ~0.9 us per block of a segment, the segments side by side; this way costs what the picture
         // costs -- clearing the buffers, two passes over the blocks: ~0.58 ms at 4K -- whatever the interval.  4K: from ~650 blocks per segment, 1080p: from ~290)
         const bool seg_parallel = wave_path && !e->force_wave_kernel && e->n_seg > 1 && !nori_off &&
-                                  0.9 * (double) e->ri * (e->nonint ? 1 : e->ybl + 2) > 150.0 + 5.2e-5 * (double) w * (double) h;
+                                  0.9 * (double) e->ri * (e->nonint ? 1 : e->ybl + e->nc) > 150.0 + 5.2e-5 * (double) w * (double) h;
         auto fill_segments = [&](const ScanPlan *scan) -> int {
-                const uint32_t per_mcu = (uint32_t) (scan ? 1 : e->ybl + 2), n_blocks = (uint32_t) e->n_mcu * per_mcu;
-                if (!e->nori_bits) UG_HIP_TRY(hipMalloc((void **) &e->nori_bits, ((size_t) e->n_mcu * (e->ybl + 2) + 1) * 4));
+                const uint32_t per_mcu = (uint32_t) (scan ? 1 : e->ybl + e->nc), n_blocks = (uint32_t) e->n_mcu * per_mcu;
+                if (!e->nori_bits) UG_HIP_TRY(hipMalloc((void **) &e->nori_bits, ((size_t) e->n_mcu * (e->ybl + e->nc) + 1) * 4));
                 if (e->nori_ff_cap < (size_t) e->n_seg + 1) {
                         if (e->nori_ff) (void) hipFree(e->nori_ff);
                         e->nori_ff = nullptr;
@@ -2217,7 +2261,8 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 for (int f = 0; f < frames; f++) {
                         NoriScan s = {};
                         s.c0 = (scan ? scan->coef : e->cy) + f * bs.coef_y; s.c1 = e->cb + f * bs.coef_c; s.c2 = e->cr + f * bs.coef_c;
-                        s.mcu_w = e->mcu_w; s.n_mcu = e->n_mcu; s.hs = scan ? 1 : e->hs; s.vs = scan ? 1 : e->vs; s.nc = scan ? 0 : 2; s.tab0 = scan ? scan->tab0 : 0; s.ctab = e->ctab; s.ri = e->ri;
+                        s.c3 = e->ca ? e->ca + f * bs.coef_c : nullptr;
+                        s.mcu_w = e->mcu_w; s.n_mcu = e->n_mcu; s.hs = scan ? 1 : e->hs; s.vs = scan ? 1 : e->vs; s.nc = scan ? 0 : e->nc; s.tab0 = scan ? scan->tab0 : 0; s.ctab = e->ctab; s.ri = e->ri;
                         uint32_t *const raw = e->scratch + (size_t) f * bs.raw_words;
                         hipLaunchKernelGGL(nori_len_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, e->nori_bits);
                         hipLaunchKernelGGL(nori_segscan_kernel, dim3(1), dim3(1024), 0, st, e->nori_bits, n_blocks, (uint32_t) e->ri * per_mcu, e->nori_ff);
@@ -2235,7 +2280,8 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 // its header bytes (scan 0: SOI .. SOS; scans 1, 2: their SOS).  Where a scan ends is only known once it is coded: the launch of scan c
                 // reads the length scan c - 1 left behind (CodeArgs::base) and goes on from there, over the EOI every coded stream ends with.  Three
                 // launches on the stream, one synchronisation, no intermediate buffer.
-                memset(e->total_host, 0, 4 * kTotalWords * 4);
+                const int n_scans = 1 + e->nc;
+                memset(e->total_host, 0, (size_t) (1 + n_scans) * kTotalWords * 4);
                 if (wave_path && frames > e->raw_cap) {
                         const hipError_t err = alloc_raw(e, e->batch_cap);
                         if (err != hipSuccess) {
@@ -2244,8 +2290,9 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                                 return UG_HIP_ERUNTIME;
                         }
                 }
-                for (int c = 0; c < 3; c++) {
-                        const ScanPlan pl = { c == 0 ? e->cy : (c == 1 ? e->cb : e->cr), e->ycc && c > 0 ? 1 : 0, e->scan_header_dev[c], (int) e->scan_header[c].size(),
+                for (int c = 0; c < n_scans; c++) {
+                        const int16_t *const planes[4] = { e->cy, e->cb, e->cr, e->ca };
+                        const ScanPlan pl = { planes[c], e->ycc && c > 0 ? 1 : 0, e->scan_header_dev[c], (int) e->scan_header[c].size(),
                                               c > 0 ? e->total_host_dev + c * kTotalWords : nullptr, e->total_host_dev + (c + 1) * kTotalWords };
                         if (nori) {
                                 const int nrc = code_without_restart(&pl);
@@ -2258,7 +2305,7 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                                         const int frc = fill_segments(&pl);
                                         if (frc != UG_HIP_SUCCESS) return frc;
                                 } else {
-                                        hipLaunchKernelGGL(entropy_wave_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, pl.coef, pl.coef, pl.coef, e->mcu_w, e->n_mcu, 1, 1,
+                                        hipLaunchKernelGGL(entropy_wave_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, pl.coef, pl.coef, pl.coef, pl.coef, e->mcu_w, e->n_mcu, 1, 1,
                                                            0, 0, pl.tab0, e->ri, e->n_seg, e->scratch, e->cap / 4, e->seg_len, e->seg_ff, e->chunk_tot, bs);
                                 }
                                 hipLaunchKernelGGL(compact_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, (const uint8_t *) e->scratch, e->cap, e->seg_len, e->seg_ff,
@@ -2270,8 +2317,10 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 }
                 UG_HIP_LAUNCH_CHECK();
                 UG_HIP_TRY(hipStreamSynchronize(st));
-                const uint32_t *const t1 = e->total_host + kTotalWords, *const t2 = t1 + kTotalWords, *const t3 = t2 + kTotalWords;
-                if (t1[kMaxBatch] | t2[kMaxBatch] | t3[kMaxBatch]) { // a workgroup gave up waiting for an earlier one (see below): start-order tickets, once more
+                const uint32_t *const t_last = e->total_host + n_scans * kTotalWords; // the last scan's length words
+                uint32_t gave_up = 0;
+                for (int c = 1; c <= n_scans; c++) gave_up |= e->total_host[c * kTotalWords + kMaxBatch];
+                if (gave_up) { // a workgroup gave up waiting for an earlier one (see below): start-order tickets, once more
                         (void) hipMemset(e->ticket, 0, 4);
                         if (!e->use_ticket) {
                                 e->use_ticket = true;
@@ -2284,7 +2333,7 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 }
                 bool fits = true;
                 for (int f = 0; f < frames; f++) {
-                        out_len[f] = t3[f]; // the last scan's end = the stream's length (what it needs, when it does not fit: nothing past the capacity was written)
+                        out_len[f] = t_last[f]; // the last scan's end = the stream's length (what it needs, when it does not fit: nothing past the capacity was written)
                         fits = fits && out_len[f] <= out_capacity;
                 }
                 if (!fits && frames == 1) {
@@ -2318,8 +2367,8 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                         const int frc = fill_segments(nullptr);
                         if (frc != UG_HIP_SUCCESS) return frc;
                 } else {
-                hipLaunchKernelGGL(entropy_wave_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, e->cy, e->cb, e->cr, e->mcu_w, e->n_mcu, e->hs, e->vs,
-                                   e->ctab, 2, 0, e->ri, e->n_seg, e->scratch, e->cap / 4, e->seg_len, e->seg_ff, e->chunk_tot, bs);
+                hipLaunchKernelGGL(entropy_wave_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, e->cy, e->cb, e->cr, e->ca ? e->ca : e->cr, e->mcu_w, e->n_mcu,
+                                   e->hs, e->vs, e->ctab, e->nc, 0, e->ri, e->n_seg, e->scratch, e->cap / 4, e->seg_len, e->seg_ff, e->chunk_tot, bs);
                 }
                 hipLaunchKernelGGL(compact_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, (const uint8_t *) e->scratch, e->cap, e->seg_len, e->seg_ff, e->chunk_tot,
                                    e->n_seg, (uint8_t *) out_dev, e->header_dev, (int) e->header.size(), out_capacity, e->total_host_dev, nullptr, bs);

@@ -227,6 +227,70 @@ __global__ __launch_bounds__(256) void rgb_jpeg444_kernel(const uint8_t *__restr
         }
 }
 
+// Packed RGBA (4 B/px: R, G, B, A) -> four component planes' worth of blocks (4:4:4:4) in one pass: the layout of rgb_jpeg444_kernel with a fourth
+// component -- a lane holds one 8x8 pixel block = 8 rows x 32 B in 64 registers, loaded as two aligned 16-byte words per row where the frame allows,
+// and runs the four DCTs one after another.  Each plane equals fdct_quant_plane_kernel's on that channel (xstride 4).  4 B/px read + 8 B/px written.
+__global__ __launch_bounds__(256) void rgba_jpeg4444_kernel(const uint8_t *__restrict__ src, int pitch, int width, int height, int blocks_w,
+                                                            long total, const float *__restrict__ div, int16_t *__restrict__ out0,
+                                                            int16_t *__restrict__ out1, int16_t *__restrict__ out2, int16_t *__restrict__ out3)
+{
+        __shared__ __attribute__((aligned(16))) uint8_t lds_all[4 * kStoreRows * kLdsPitch];
+        const long idx = (long) blockIdx.x * blockDim.x + threadIdx.x;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const long wave_first = idx - lane;
+        if (wave_first >= total) return; // wave-uniform
+        uint8_t *lds = lds_all + wave * kStoreRows * kLdsPitch;
+        const long left = total - wave_first;
+        const int n_valid = left < 64 ? (int) left : 64;
+        uint32_t raw[8][8]; // row r, pixel c: R | G << 8 | B << 16 | A << 24
+        if (idx < total) {
+                const int by = (int) (idx / blocks_w), bx = (int) (idx - (long) by * blocks_w);
+                const bool interior = 8 * bx + 8 <= width && 8 * by + 8 <= height;
+                if (interior && !(pitch & 15) && !(15 & (uintptr_t) src)) {
+#pragma unroll
+                        for (int r = 0; r < 8; r++) {
+                                const uint4 *p = (const uint4 *) (src + (long) (8 * by + r) * pitch + 32 * bx);
+                                const uint4 q0 = p[0], q1 = p[1];
+                                raw[r][0] = q0.x; raw[r][1] = q0.y; raw[r][2] = q0.z; raw[r][3] = q0.w;
+                                raw[r][4] = q1.x; raw[r][5] = q1.y; raw[r][6] = q1.z; raw[r][7] = q1.w;
+                        }
+                } else if (interior && !(pitch & 3) && !(3 & (uintptr_t) src)) {
+#pragma unroll
+                        for (int r = 0; r < 8; r++) {
+                                const uint32_t *p = (const uint32_t *) (src + (long) (8 * by + r) * pitch + 32 * bx);
+#pragma unroll
+                                for (int c = 0; c < 8; c++) raw[r][c] = p[c];
+                        }
+                } else { // edge replication (or an unaligned frame), byte by byte into the same register layout
+#pragma unroll
+                        for (int r = 0; r < 8; r++) {
+                                const uint8_t *row = src + (long) min(8 * by + r, height - 1) * pitch;
+#pragma unroll
+                                for (int c = 0; c < 8; c++) {
+                                        const uint8_t *px = row + 4L * min(8 * bx + c, width - 1);
+                                        raw[r][c] = (uint32_t) px[0] | (uint32_t) px[1] << 8 | (uint32_t) px[2] << 16 | (uint32_t) px[3] << 24;
+                                }
+                        }
+                }
+        }
+#pragma unroll
+        for (int comp = 0; comp < 4; comp++) {
+                uint32_t w[32];
+                if (idx < total) {
+                        float b[64];
+#pragma unroll
+                        for (int r = 0; r < 8; r++) {
+#pragma unroll
+                                for (int c = 0; c < 8; c++) b[8 * r + c] = (float) ((raw[r][c] >> (8 * comp)) & 0xff);
+                        }
+                        fdct8x8(b);
+                        quant_pack(b, div, w);
+                }
+                wave_store_blocks(w, lds, (comp == 0 ? out0 : (comp == 1 ? out1 : (comp == 2 ? out2 : out3))) + 64 * wave_first, lane, n_valid);
+                __builtin_amdgcn_wave_barrier(); // the LDS region is reused by the next component
+        }
+}
+
 // batches: frame f reads src + f * src bytes and writes its coefficient planes f * luma / chroma bytes further on
 struct FrameStrides {
         size_t src, luma, chroma; // bytes
@@ -501,6 +565,26 @@ int ug::jpeg_fdct_quant_rgb444(const void *src, int pitch, int width, int height
         const long total = (long) blocks_w * blocks_h;
         hipLaunchKernelGGL(rgb_jpeg444_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, (hipStream_t) stream,
                            (const uint8_t *) src, pitch, width, height, blocks_w, total, div, out_r, out_g, out_b);
+        UG_HIP_LAUNCH_CHECK();
+        return UG_HIP_SUCCESS;
+}
+
+// packed RGBA (4 B/px) -> quantised blocks of the R, G, B and A components, all with the divisors `div` (64 floats); declared in jpeg_entropy.hip
+namespace ug {
+int jpeg_fdct_quant_rgba4444(const void *src, int pitch, int width, int height, int blocks_w, int blocks_h, const float *div,
+                             int16_t *out_r, int16_t *out_g, int16_t *out_b, int16_t *out_a, ug_hip_stream_t stream);
+}
+int ug::jpeg_fdct_quant_rgba4444(const void *src, int pitch, int width, int height, int blocks_w, int blocks_h, const float *div,
+                                 int16_t *out_r, int16_t *out_g, int16_t *out_b, int16_t *out_a, ug_hip_stream_t stream)
+{
+        if (!src || !div || !out_r || !out_g || !out_b || !out_a || width <= 0 || height <= 0 || blocks_w * 8 < width || blocks_h * 8 < height ||
+            (15 & ((uintptr_t) out_r | (uintptr_t) out_g | (uintptr_t) out_b | (uintptr_t) out_a)) || pitch < 4 * width) {
+                ug::set_last_error_msg("jpeg_fdct_quant_rgba4444: bad arguments");
+                return UG_HIP_EINVAL;
+        }
+        const long total = (long) blocks_w * blocks_h;
+        hipLaunchKernelGGL(rgba_jpeg4444_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, (hipStream_t) stream,
+                           (const uint8_t *) src, pitch, width, height, blocks_w, total, div, out_r, out_g, out_b, out_a);
         UG_HIP_LAUNCH_CHECK();
         return UG_HIP_SUCCESS;
 }

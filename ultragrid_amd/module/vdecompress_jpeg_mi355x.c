@@ -108,7 +108,8 @@ static decompress_status probe_internal_codec(unsigned char *buffer, size_t len,
         if (internal_prop != NULL) {
                 internal_prop->depth = 8;
                 internal_prop->rgb = rgb != 0;
-                internal_prop->subsampling = sub == 444 ? 4440 : (sub == 422 ? 4220 : (sub == 420 ? 4200 : 4000));
+                // 4444: R, G, B + alpha (GPUJPEG_4444_U8_P0123, gpujpeg.c:255-259), reported RGB like the reference does
+                internal_prop->subsampling = sub == 4444 ? 4444 : (sub == 444 ? 4440 : (sub == 422 ? 4220 : (sub == 420 ? 4200 : 4000)));
         }
         return DECODER_GOT_CODEC;
 }
