@@ -243,6 +243,43 @@ int ug_hip_selftest_dxt_encode(unsigned *mismatches, ug_hip_stream_t stream);
  * reference's full form for all of its blocks.  Returns the number of such waves since the last reset on the current device:
  * [0] colour stage, [1] alpha stage.  Synchronises the device. */
 int ug_hip_dxt_encode_stats(unsigned long long full_form_waves[2], int reset);
+/* Diagnostics (tests, profiling): what the last call of an LDGM session (below) issued -- kernel launches, host <-> device copies (the
+ * schedule upload included) and levels of its decode schedule.  Any pointer may be NULL.  Does not touch the device. */
+typedef struct ug_hip_ldgm ug_hip_ldgm;
+int ug_hip_ldgm_stats(const ug_hip_ldgm *s, int *launches, int *copies, int *levels);
+
+/* ------------------------------------------------------------------------------------
+ * LDGM forward error correction (replaces ldgm/src/ldgm-session-gpu.cpp + gpu.cu; the coder of src/rtp/ldgm.cpp)
+ * ---------------------------------------------------------------------------------- */
+/* A session holds one parity-check matrix on one device: `pcm` is m rows of w_f ints padded with -1 (LDGM_session::set_pcMatrix,
+ * ldgm-session.cpp:40-121); row r lists its data packets (< k), then parity packets k + r and k + r - 1.  k 1..8191, m 1..65535, w_f 2..128,
+ * every entry in [-1, k + m): anything else is refused with UG_HIP_EINVAL before the device is touched (so is a NULL pointer).
+ * A buffer is k data packets of ps bytes followed by m parity packets; ps must be a positive multiple of 4 up to 65535 (LDGM_session's
+ * packet_size is an unsigned short), else UG_HIP_EINVAL before any device call.  Calls switch to the session's device and back.
+ * One session serves one call at a time; distinct sessions may run on distinct streams (and threads) at once.  Buffers the session keeps
+ * for itself grow with the largest ps seen (hipMalloc: that call synchronises the device). */
+int  ug_hip_ldgm_create(int device, int k, int m, const int *pcm, int w_f, ug_hip_ldgm **out);
+void ug_hip_ldgm_destroy(ug_hip_ldgm *s); /* waits for the session's last schedule upload; NULL: nothing to do */
+/* Encode: parity = the staircase of LDGM_session_cpu::encode (ldgm-session-cpu.cpp:152), byte for byte, written over the parity region of
+ * `buf_dev` ((k + m) x ps bytes of device memory).  Two kernel launches on `stream`, asynchronous. */
+int  ug_hip_ldgm_encode(ug_hip_ldgm *s, void *buf_dev, int ps, ug_hip_stream_t stream);
+/* Decode in place on the device.  received[i] != 0: packet i (k + m of them) arrived whole.  The packets that can be recovered are found on
+ * the host by peeling to the fixpoint (LDGM_session_cpu::decode_frame stops after 4 sweeps: this recovers every packet those do, and
+ * possibly more); only the recoveries that missing data packets need are run, one kernel launch per level of the schedule, asynchronous on
+ * `stream`.  recovered (k + m bytes, may be NULL) = 1 for each packet written: the recovered data packets and the parity packets rebuilt on
+ * the way.  *all_data_known (may be NULL) = every data packet arrived or was recovered.  Packets that arrived are never written; missing
+ * packets that are not recovered keep whatever the buffer held.  No data packet missing, or none recoverable: no device work at all.
+ * The schedule goes up through a pinned staging buffer of the session: a call waits for the previous call's upload of it. */
+int  ug_hip_ldgm_decode(ug_hip_ldgm *s, void *buf_dev, int ps, const uint8_t *received, uint8_t *recovered, int *all_data_known,
+                        ug_hip_stream_t stream);
+/* Host-buffer forms (the ldgm_gpu plugin): the same on a host buffer of (k + m) x ps bytes (pinned memory is copied fastest), through a
+ * device buffer of the session.  Both synchronise `stream` before they return.
+ *   encode_host: uploads the k x ps data bytes, downloads the m x ps parity bytes into buf_host.
+ *   decode_host: with a data packet missing and recoverable, uploads the buffer, runs the schedule and downloads the recovered data
+ *                packets only (gathered into one copy) into their places in buf_host; otherwise does nothing on the device. */
+int  ug_hip_ldgm_encode_host(ug_hip_ldgm *s, void *buf_host, int ps, ug_hip_stream_t stream);
+int  ug_hip_ldgm_decode_host(ug_hip_ldgm *s, void *buf_host, int ps, const uint8_t *received, uint8_t *recovered, int *all_data_known,
+                             ug_hip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Pixel-format conversion, whole frame on the device (replaces the decoder_t line loop,

@@ -9,7 +9,7 @@ set -e
 UG=${1:?usage: install.sh <ultragrid-source-dir>}
 HERE=$(cd "$(dirname "$0")" && pwd); ROOT=$(dirname "$HERE"); M=$ROOT/ultragrid_amd/module
 test -f "$UG/configure.ac" || { echo "$UG: no configure.ac there" >&2; exit 1; }
-mkdir -p "$UG/include" "$UG/src/video_compress" "$UG/src/video_decompress" "$UG/src/libavcodec"
+mkdir -p "$UG/include" "$UG/src/video_compress" "$UG/src/video_decompress" "$UG/src/libavcodec" "$UG/src/rtp"
 cp "$ROOT/include/ug_mi355x.h"               "$UG/include/ug_mi355x.h"
 cp "$M/vcompress_dxt_mi355x.cpp"             "$UG/src/video_compress/dxt_mi355x.cpp"
 cp "$M/vcompress_jpeg_mi355x.cpp"            "$UG/src/video_compress/jpeg_mi355x.cpp"
@@ -19,9 +19,11 @@ cp "$M/vdecompress_jpeg_mi355x.c"            "$UG/src/video_decompress/jpeg_mi35
 cp "$M/vdecompress_jpeg_to_dxt_mi355x.c"     "$UG/src/video_decompress/jpeg_to_dxt_mi355x.c"
 cp "$M/mi355x_receiver.h"                    "$UG/src/video_decompress/"
 cp "$M/lavc_conv_mi355x.cpp"                 "$UG/src/libavcodec/lavc_conv_mi355x.cpp"
+cp "$M/ldgm_gpu_mi355x.cpp"                  "$UG/src/rtp/ldgm_gpu_mi355x.cpp"
+cp "$M/mi355x_receiver.h"                    "$UG/src/rtp/"
 if grep -q "found_ug_mi355x" "$UG/configure.ac"; then
         echo "configure.ac is patched already"
 else
         patch -p1 -d "$UG" < "$HERE/ultragrid_mi355x.patch"
 fi
-echo "installed into $UG: 5 modules + the lavc hook; configure with --with-ug-mi355x=<prefix>"
+echo "installed into $UG: 5 modules, the lavc hook and the ldgm_gpu library; configure with --with-ug-mi355x=<prefix>"

@@ -7,7 +7,10 @@ four insertions into configure.ac, nothing removed --
   2. the lavc conversion hook: HAVE_LAVC_CUDA_CONV with src/libavcodec/lavc_conv_mi355x.o in place of the two stubbed *_cuda.o objects
      (configure.ac:2056-2069 of the reference; the hook's declarations are the reference's own *_cuda.h headers),
   3. the five modules through the reference's add_module helper (configure.ac:243-259), behind the CUDA DXT section,
-  4. a line in the summary table.
+  4. a line in the summary table,
+  5. the ldgm_gpu library (src/rtp/ldgm_gpu_mi355x.o) where LDGM is on and the CUDA ldgm_gpu is not built: in front of the LDGM GPU
+     section's ENSURE_FEATURE_PRESENT, so that --enable-ldgm-gpu without CUDA succeeds when libug_mi355x is found (the detection of 1.
+     runs earlier in configure.ac than the LDGM section).
 Only `diff -u` context lines of the reference appear in the patch; no reference source is copied into this repository.
 """
 import difflib, os, sys
@@ -66,6 +69,16 @@ fi
 ENSURE_FEATURE_PRESENT([$ug_mi355x_req], [$ug_mi355x], [libug_mi355x not found])
 '''
 
+LDGM = '''if test "${ldgm_gpu?}" != yes && test "${ldgm_gpu_req?}" != no && test "${ldgm?}" = yes &&
+        test "${found_ug_mi355x?}" = yes
+then
+        # GPU LDGM on the MI355X (libug_mi355x), where the CUDA one above was not built
+        add_module ldgm_gpu "src/rtp/ldgm_gpu_mi355x.o" "$UG_MI355X_LIB"
+        ldgm_gpu=yes
+fi
+
+'''
+
 SUMMARY = 'add_column "MI355X DXT/JPEG" "${ug_mi355x?}"\n'
 
 
@@ -98,6 +111,8 @@ def main():
     new = insert_before(new, "        AC_DEFINE([HAVE_LAVC], [1], [Build with LAVC support])", LAVC)
     # 3. behind the CUDA DXT section
     new = insert_after(new, "ENSURE_FEATURE_PRESENT([$cuda_dxt_req], [$cuda_dxt], [CUDA DXT not found])", MODULES)
+    # 5. the MI355X ldgm_gpu, in front of the LDGM GPU section's check
+    new = insert_before(new, "ENSURE_FEATURE_PRESENT([$ldgm_gpu_req], [$ldgm_gpu], [LDGM accelerated GPU cannot be enabled (CUDA not found?)])", LDGM)
     # 4. summary table, behind "Lavc ..." keeps the list alphabetical enough: in front of OpenAPV
     new = insert_before(new, 'add_column "OpenAPV" "${openapv?}"', SUMMARY)
     diff = difflib.unified_diff(orig, new, "a/configure.ac", "b/configure.ac", n=3)

@@ -413,3 +413,62 @@ class JpegDecoder:
             self.close()
         except Exception:
             pass
+
+
+class LdgmCoder:
+    """ug_hip_ldgm_* (LDGM_session_gpu's encode / decode_frame, ldgm/src/ldgm-session-gpu.h): one parity-check matrix on one device.
+    pcm: (m, w_f) int32 array, rows padded with -1.  Buffers are torch uint8 device tensors of (k + m) * ps bytes."""
+
+    def __init__(self, k: int, m: int, pcm, device: int | None = None):
+        import numpy as np
+        pcm = np.ascontiguousarray(pcm, dtype=np.int32)
+        if pcm.ndim != 2 or pcm.shape[0] != m:
+            raise ValueError("pcm must be an (m, w_f) array")
+        self.k, self.m, self.wf = k, m, pcm.shape[1]
+        self.device = torch.cuda.current_device() if device is None else device
+        self._pcm = pcm
+        self._h = C.c_void_p()
+        L.check(L.load().ug_hip_ldgm_create(self.device, k, m, pcm.ctypes.data, self.wf, C.byref(self._h)), "ug_hip_ldgm_create")
+
+    def _buf(self, buf: torch.Tensor) -> int:
+        buf = _u8(buf)
+        n = buf.numel()
+        if n % (self.k + self.m) != 0:
+            raise ValueError("buffer size must be (k + m) * ps")
+        return n // (self.k + self.m)
+
+    def encode(self, buf: torch.Tensor) -> torch.Tensor:
+        """Writes the parity region of buf in place (asynchronous on the current stream); returns buf."""
+        ps = self._buf(buf)
+        L.check(L.load().ug_hip_ldgm_encode(self._h, buf.data_ptr(), ps, _stream()), "ug_hip_ldgm_encode")
+        return buf
+
+    def decode(self, buf: torch.Tensor, received):
+        """received: k + m flags (packet arrived whole).  Recovers in place; returns (recovered flags as numpy bool, all data known)."""
+        import numpy as np
+        ps = self._buf(buf)
+        rx = np.ascontiguousarray(received, dtype=np.uint8)
+        if rx.shape != (self.k + self.m,):
+            raise ValueError("received must hold k + m flags")
+        rec = np.zeros(self.k + self.m, np.uint8)
+        ok = C.c_int(0)
+        L.check(L.load().ug_hip_ldgm_decode(self._h, buf.data_ptr(), ps, rx.ctypes.data, rec.ctypes.data, C.byref(ok), _stream()),
+                "ug_hip_ldgm_decode")
+        return rec.astype(bool), bool(ok.value)
+
+    def stats(self) -> dict:
+        """launches, copies and schedule levels of the session's last call"""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        L.check(L.load().ug_hip_ldgm_stats(self._h, C.byref(a), C.byref(b), C.byref(c)), "ug_hip_ldgm_stats")
+        return dict(launches=a.value, copies=b.value, levels=c.value)
+
+    def close(self):
+        if self._h:
+            L.load().ug_hip_ldgm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
