@@ -73,6 +73,10 @@ typedef enum {
         UG_PF_Y416 = 14,    /* 16-bit 4:4:4:4  U Y V A */
         UG_PF_VUYA = 15,    /* 8-bit 4:4:4:4  V U Y A */
         UG_PF_DVS10 = 16,   /* 10-bit 4:2:2 of DVS cards, 6 px / 16 B like v210 */
+        /* an OUTPUT of ug_hip_pixfmt_convert[_batch] from UG_PF_RGB / UG_PF_RGBA only, no codec of its own (never an input, never a
+         * ug_hip_pixfmt_best answer): UYVY bytes as dxt_compress/rgba_to_yuv422.glsl computes them -- the shader of `-c uyvy`
+         * (src/video_compress/uyvy.cpp) -- lines of vc_get_linesize(width, UYVY) bytes */
+        UG_PF_UYVY_GL = 17,
 } ug_pixfmt_t;
 
 typedef enum {
@@ -292,7 +296,10 @@ int ug_hip_pixfmt_supported(ug_pixfmt_t in, ug_pixfmt_t out);
  * those reachable from `in`.  UG_HIP_EUNSUPP if none is reachable. */
 int ug_hip_pixfmt_best(ug_pixfmt_t in, const ug_pixfmt_t *candidates, ug_pixfmt_t *out);
 /* rshift/gshift/bshift have decoder_t meaning (honoured for RGBA / RGB outputs, defaults
- * 0/8/16, pixfmt_conv.h:62-65).  Pitches 0 = vc_get_linesize(). */
+ * 0/8/16, pixfmt_conv.h:62-65).  Pitches 0 = vc_get_linesize().
+ * out = UG_PF_UYVY_GL (in = UG_PF_RGB or UG_PF_RGBA; any other input, or UG_PF_UYVY_GL as input: UG_HIP_EUNSUPP): output pixel pair i of
+ * a line = rgba_to_yuv422.glsl's fp32 arithmetic on pixels 2i and 2i + 1 (for odd widths the last pair repeats the last pixel, GL's
+ * CLAMP_TO_EDGE), float -> unorm8 with ties to even, alpha ignored, lines read at the given pitch (packed: 3 / 4 bytes per pixel). */
 int ug_hip_pixfmt_convert(ug_pixfmt_t in, ug_pixfmt_t out, const void *src_dev, void *dst_dev,
                           int width, int height, int src_pitch, int dst_pitch,
                           int rshift, int gshift, int bshift, ug_hip_stream_t stream);

@@ -13,6 +13,7 @@ mkdir -p "$UG/include" "$UG/src/video_compress" "$UG/src/video_decompress" "$UG/
 cp "$ROOT/include/ug_mi355x.h"               "$UG/include/ug_mi355x.h"
 cp "$M/vcompress_dxt_mi355x.cpp"             "$UG/src/video_compress/dxt_mi355x.cpp"
 cp "$M/vcompress_jpeg_mi355x.cpp"            "$UG/src/video_compress/jpeg_mi355x.cpp"
+cp "$M/vcompress_uyvy_mi355x.cpp"            "$UG/src/video_compress/uyvy_mi355x.cpp"
 cp "$M/ug_codec_map.h" "$M/mi355x_frame_sharder.h" "$UG/src/video_compress/"
 cp "$M/vdecompress_dxt_mi355x.c"             "$UG/src/video_decompress/dxt_mi355x.c"
 cp "$M/vdecompress_jpeg_mi355x.c"            "$UG/src/video_decompress/jpeg_mi355x.c"
@@ -26,4 +27,4 @@ if grep -q "found_ug_mi355x" "$UG/configure.ac"; then
 else
         patch -p1 -d "$UG" < "$HERE/ultragrid_mi355x.patch"
 fi
-echo "installed into $UG: 5 modules, the lavc hook and the ldgm_gpu library; configure with --with-ug-mi355x=<prefix>"
+echo "installed into $UG: 6 modules, the lavc hook and the ldgm_gpu library; configure with --with-ug-mi355x=<prefix>"

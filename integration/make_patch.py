@@ -6,7 +6,8 @@ four insertions into configure.ac, nothing removed --
   1. detection of libug_mi355x (--with-ug-mi355x=<prefix>) in front of the Libav section (that section needs the answer),
   2. the lavc conversion hook: HAVE_LAVC_CUDA_CONV with src/libavcodec/lavc_conv_mi355x.o in place of the two stubbed *_cuda.o objects
      (configure.ac:2056-2069 of the reference; the hook's declarations are the reference's own *_cuda.h headers),
-  3. the five modules through the reference's add_module helper (configure.ac:243-259), behind the CUDA DXT section,
+  3. the six modules through the reference's add_module helper (configure.ac:243-259), behind the CUDA DXT section -- where rtdxt, uyvy
+     and cuda_dxt are decided -- with MI355X_NO_UYVY_COMPRESS / MI355X_NO_RTDXT / MI355X_NO_CUDA_DXT defined for those configure left out,
   4. a line in the summary table,
   5. the ldgm_gpu library (src/rtp/ldgm_gpu_mi355x.o) where LDGM is on and the CUDA ldgm_gpu is not built: in front of the LDGM GPU
      section's ENSURE_FEATURE_PRESENT, so that --enable-ldgm-gpu without CUDA succeeds when libug_mi355x is found (the detection of 1.
@@ -54,7 +55,7 @@ LAVC = '''        if test "$lavc_cuda" != yes && test "$found_ug_mi355x" = yes; 
 
 MODULES = '''
 # -------------------------------------------------------------------------------------------------
-# MI355X DXT / JPEG compression and decompression (-c dxt, -c jpeg; needs no CUDA, no GL context)
+# MI355X DXT / JPEG / UYVY compression and DXT / JPEG decompression (-c dxt, -c jpeg, -c uyvy_mi355x; needs no CUDA, no GL context)
 # -------------------------------------------------------------------------------------------------
 if test "${found_ug_mi355x?}" = yes
 then
@@ -64,6 +65,18 @@ then
         add_module vdecompress_dxt_mi355x "src/video_decompress/dxt_mi355x.o" "$UG_MI355X_LIB"
         add_module vdecompress_jpeg_mi355x "src/video_decompress/jpeg_mi355x.o" "$UG_MI355X_LIB"
         add_module vdecompress_jpeg_to_dxt_mi355x "src/video_decompress/jpeg_to_dxt_mi355x.o" "$UG_MI355X_LIB"
+        # -c uyvy without GL (RGB / RGBA -> UYVY as the reference's shader computes it); the stand-ins take the names of the modules this
+        # configure run left out -- and only those: where a module of that name is built, its registration stays alone
+        add_module vcompress_uyvy_mi355x "src/video_compress/uyvy_mi355x.o" "$UG_MI355X_LIB"
+        if test "${uyvy?}" != yes; then
+                AC_DEFINE([MI355X_NO_UYVY_COMPRESS], [1], [uyvy_mi355x also registers as -c uyvy])
+        fi
+        if test "${rtdxt?}" != yes; then
+                AC_DEFINE([MI355X_NO_RTDXT], [1], [dxt (MI355X) also registers as -c rtdxt])
+        fi
+        if test "${cuda_dxt?}" != yes; then
+                AC_DEFINE([MI355X_NO_CUDA_DXT], [1], [dxt (MI355X) also registers as -c cuda_dxt])
+        fi
 fi
 
 ENSURE_FEATURE_PRESENT([$ug_mi355x_req], [$ug_mi355x], [libug_mi355x not found])

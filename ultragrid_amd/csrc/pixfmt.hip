@@ -12,6 +12,11 @@
 //     wave accesses contiguous -- these are pure HBM-bandwidth kernels.
 #include "ug_common.h"
 
+namespace ug {
+// uyvy_gl.hip: RGB / RGBA -> UG_PF_UYVY_GL (rgba_to_yuv422.glsl)
+int uyvy_gl_convert(ug_pixfmt_t in, const void *src, void *dst, int width, int height, int src_pitch, int dst_pitch, hipStream_t stream);
+} // namespace ug
+
 namespace {
 
 // Q14 coefficients, BT.709 limited range (the default, color_space.c:149-191).  Values are the
@@ -520,11 +525,15 @@ bool try_fast(const Args &a, hipStream_t st, int &rc)
         return true;
 }
 
+// vc_get_linesize, with UG_PF_UYVY_GL (lines of UYVY) added
+int line_size(ug_pixfmt_t f, int width) { return ug::linesize(f == UG_PF_UYVY_GL ? UG_PF_UYVY : f, width); }
+
 int size_of(ug_pixfmt_t f, int width) // vc_get_size, video_codec.c:530-538
 {
         switch (f) {
         case UG_PF_RGBA: return width * 4;
         case UG_PF_UYVY:
+        case UG_PF_UYVY_GL:
         case UG_PF_YUYV: return (width + 1) / 2 * 4;
         case UG_PF_RGB:
         case UG_PF_BGR: return width * 3;
@@ -731,6 +740,8 @@ extern "C" {
 
 int ug_hip_pixfmt_supported(ug_pixfmt_t in, ug_pixfmt_t out)
 {
+        if (out == UG_PF_UYVY_GL) return in == UG_PF_RGB || in == UG_PF_RGBA; // (rgba_to_yuv422.glsl, uyvy_gl.hip: not a decoders[] pair)
+        if (in == UG_PF_UYVY_GL) return 0;
         if (in == out && in != UG_PF_NONE && size_of(in, 2) != 0) return 1;
         if (ug::pixfmt_ext_supported(in, out)) return 1;
         switch (PAIR(in, out)) {
@@ -762,7 +773,7 @@ int ug_hip_pixfmt_convert_batch(ug_pixfmt_t in, ug_pixfmt_t out, const void *src
                 return UG_HIP_EINVAL;
         }
         if (frames == 0) return UG_HIP_SUCCESS;
-        const int sp = src_pitch ? src_pitch : ug::linesize(in, width), dp = dst_pitch ? dst_pitch : ug::linesize(out, width);
+        const int sp = src_pitch ? src_pitch : ug::linesize(in, width), dp = dst_pitch ? dst_pitch : line_size(out, width);
         if (sp <= 0 || dp <= 0) {
                 ug::set_last_error_msg("ug_hip_pixfmt_convert_batch: unsupported format");
                 return UG_HIP_EUNSUPP;
@@ -787,7 +798,7 @@ int ug_hip_pixfmt_convert(ug_pixfmt_t in, ug_pixfmt_t out, const void *src, void
 {
         if (!ug::dims_ok(width, height)) return ug::refuse_size("ug_hip_pixfmt_convert");
         if (src_pitch < 0 || dst_pitch < 0 || !ug::span_ok(src_pitch ? src_pitch : ug::linesize(in, width), height) ||
-            !ug::span_ok(dst_pitch ? dst_pitch : ug::linesize(out, width), height)) {
+            !ug::span_ok(dst_pitch ? dst_pitch : line_size(out, width), height)) {
                 return ug::refuse_size("ug_hip_pixfmt_convert");
         }
         return pixfmt_convert_lines(in, out, src, dst, width, height, src_pitch, dst_pitch, rshift, gshift, bshift, stream);
@@ -817,13 +828,14 @@ static int pixfmt_convert_lines(ug_pixfmt_t in, ug_pixfmt_t out, const void *src
         Args a;
         a.src = (const uint8_t *) src; a.dst = (uint8_t *) dst; a.width = width; a.height = height;
         a.spitch = src_pitch ? src_pitch : ug::linesize(in, width);
-        a.dpitch = dst_pitch ? dst_pitch : ug::linesize(out, width);
+        a.dpitch = dst_pitch ? dst_pitch : line_size(out, width);
         a.dst_len = size_of(out, width);
         a.src_line = ug::linesize(in, width);
         a.rs = rshift; a.gs = gshift; a.bs = bshift;
         hipStream_t st = (hipStream_t) stream;
         int rc = UG_HIP_SUCCESS;
 
+        if (out == UG_PF_UYVY_GL) return ug::uyvy_gl_convert(in, src, dst, width, height, a.spitch, a.dpitch, st);
         if (in == out && out != UG_PF_RGBA && out != UG_PF_RGB) { // get_decoder_from_to, pixfmt_conv.c:3111-3114
                 return launch_generic<Copy>(a, st);
         }

@@ -325,7 +325,7 @@ int ug_hip_download_ordered(int device, void *dst_host, const void *src_dev, siz
 
 int ug_hip_linesize(ug_pixfmt_t fmt, int width)
 {
-        const int ls = ug::linesize(fmt, width); // 0: unknown format, or a width outside 1..65536 (never a wrapped int)
+        const int ls = ug::linesize(fmt == UG_PF_UYVY_GL ? UG_PF_UYVY : fmt, width); // 0: unknown format, or a width outside 1..65536 (never a wrapped int)
         if (ls <= 0) {
                 ug::set_last_error_msg("ug_hip_linesize: unknown pixel format, or width outside 1..65536");
                 return UG_HIP_EINVAL;

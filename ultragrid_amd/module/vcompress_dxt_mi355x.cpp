@@ -35,6 +35,9 @@
 #include <string>
 #include <vector>
 
+#ifdef HAVE_CONFIG_H
+#include "config.h" // MI355X_NO_RTDXT, MI355X_NO_CUDA_DXT (integration/ultragrid_mi355x.patch)
+#endif
 #include "debug.h"
 #include "host.h"
 #include "lib_common.h"
@@ -481,5 +484,15 @@ const struct video_compress_info dxt_mi355x_info = {
 
 // "dxt" is a free name in the reference (it registers rtdxt, cuda_dxt, gpujpeg/jpeg)
 REGISTER_MODULE(dxt, &dxt_mi355x_info, LIBRARY_CLASS_VIDEO_COMPRESS, VIDEO_COMPRESS_ABI_VERSION);
+// The reference's own names (dxt_glsl.cpp:332 "rtdxt", cuda_dxt.cpp:290 "cuda_dxt"; the registry matches names case-insensitively, so
+// -c RTDXT:DXT5 as well), each taken only in a build that lacks the module of that name -- the configure patch defines MI355X_NO_RTDXT /
+// MI355X_NO_CUDA_DXT where configure decided rtdxt=no / cuda_dxt=no; where the module is built nothing of the reference's registry changes.
+// The option forms DXT1, DXT5 and DXT1_YUV are this module's own.
+#ifdef MI355X_NO_RTDXT
+REGISTER_HIDDEN_MODULE(rtdxt, &dxt_mi355x_info, LIBRARY_CLASS_VIDEO_COMPRESS, VIDEO_COMPRESS_ABI_VERSION);
+#endif
+#ifdef MI355X_NO_CUDA_DXT
+REGISTER_HIDDEN_MODULE(cuda_dxt, &dxt_mi355x_info, LIBRARY_CLASS_VIDEO_COMPRESS, VIDEO_COMPRESS_ABI_VERSION);
+#endif
 
 } // end of anonymous namespace
