@@ -544,8 +544,16 @@ int    ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in
  * JPEG decoder (receive side: gpujpeg_decoder_create / _decode / _destroy behind
  * src/video_decompress/gpujpeg.c:74-140,292-301)
  * ---------------------------------------------------------------------------------- */
-/* Baseline JPEG (8-bit, Huffman; 3 components at 4:4:4 / 4:2:2 / 4:2:0, or 4 at 4:4:4:4, interleaved or one scan per component; restart intervals make the
- * entropy-coded data parallel: one lane per restart segment) -> `out` in device memory:
+/* Baseline JPEG (8-bit, Huffman; 1 component, 3 components, or 4 at 4:4:4:4, interleaved or one scan per component; restart intervals make the
+ * entropy-coded data parallel: one lane per restart segment) -> `out` in device memory.
+ * Three-component sampling: factors H, V of 1, 2 or 4, at most 10 blocks in an interleaved MCU, component 0 (Y' or R) at the full resolution,
+ * components 1 and 2 with the same factors at a ratio to it of 1x1, 2x1, 2x2, 1x2, 4x1 or 4x2 (read_info: 444, 422, 420, 440, 411, 410),
+ * Y'CbCr and R,G,B alike; anything else UG_HIP_EUNSUPP before any device work.  4:4:4 / 4:2:2 / 4:2:0 at their usual factors (luma 1x1, 2x1,
+ * 2x2, chroma 1x1) and 4:4:4 R,G,B take the paths below; every other layout one kernel (layout_pack_kernel) by REPLICATION -- a component
+ * sample covers its rx x ry pixels, unpinned towards libgpujpeg: R,G,B -> RGB / RGBA packed as below, -> UYVY with vc_copylineRGBtoUYVY's
+ * arithmetic on the pixel pair; Y'CbCr -> UYVY with the pair's chroma (a + b) / 2 (4:4:0 is averaged, 4:2:2-like ratios hand their samples
+ * back), -> RGB / RGBA through that UYVY; I420 stays for 4:2:0 streams.  Odd widths: the last pair's second pixel is its first.
+ *   Per layout:
  *   YCbCr streams -> UG_PF_UYVY (4:2:2: samples as they are; 4:2:0: chroma lines repeated, yuv420p_to_uyvy; 4:4:4: chroma pairs averaged),
  *                    UG_PF_RGB / UG_PF_RGBA (the UYVY form through vc_copylineUYVYtoRGB[A]: BT.709 limited range, as UltraGrid codes it),
  *                    UG_PF_I420 (4:2:0 streams: planes back to back);
@@ -567,7 +575,8 @@ int    ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in
 typedef struct ug_hip_jpeg_decoder ug_hip_jpeg_decoder;
 int  ug_hip_jpeg_decoder_create(ug_hip_jpeg_decoder **out);
 void ug_hip_jpeg_decoder_destroy(ug_hip_jpeg_decoder *dec);
-/* header only: subsampling = 444 / 422 / 420 / 400 (greyscale) / 4444 (R, G, B, A; is_rgb = 1); any pointer may be NULL */
+/* header only: subsampling = 444 / 422 / 420 / 440 / 411 / 410 (the chroma's ratio to the full resolution, as above) / 400 (greyscale) /
+ * 4444 (R, G, B, A; is_rgb = 1); any pointer may be NULL */
 int  ug_hip_jpeg_read_info(const void *jpeg_host, size_t len, int *width, int *height, int *subsampling, int *is_rgb, int *restart_interval);
 int  ug_hip_jpeg_decoder_decode(ug_hip_jpeg_decoder *dec, const void *jpeg_host, size_t len, ug_pixfmt_t out, void *dst_dev, int dst_pitch,
                                 int rshift, int gshift, int bshift, ug_hip_stream_t stream);

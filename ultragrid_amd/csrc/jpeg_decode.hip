@@ -90,6 +90,35 @@ const uint8_t kZigzagHost[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 
 __device__ const uint8_t kZigzagDev[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63 };
 
+constexpr int kMaxMcuBlocks = 10; // blocks of an interleaved MCU (T.81 B.2.3)
+
+// The three-component layouts the output stage knows (T.81 A.1.1: a component's samples are the picture's at the ratio Hmax / H x Vmax / V):
+// component 0 (Y' or R) at the full resolution, components 1 and 2 with the same factors, their ratio one of 1x1, 2x1, 2x2, 1x2, 4x1, 4x2 --
+// the layouts read_info has a code for (444, 422, 420, 440, 411, 410).  With factors of 1, 2 and 4 every ratio is an integer.
+bool layout_ok(const Header &h)
+{
+        if (h.hs[0] != h.hmax || h.vs[0] != h.vmax || h.hs[1] != h.hs[2] || h.vs[1] != h.vs[2]) return false;
+        return h.vmax / h.vs[1] <= 2;
+}
+// read_info's code of a layout parse() took, from the ratio of the chroma (components 1, 2) to the full resolution
+int layout_code(const Header &h)
+{
+        if (h.ncomp == 1) return 400;
+        if (h.ncomp == 4) return 4444;
+        const int rx = h.hmax / h.hs[1], ry = h.vmax / h.vs[1];
+        return rx == 1 ? (ry == 1 ? 444 : 440) : (rx == 2 ? (ry == 1 ? 422 : 420) : (ry == 1 ? 411 : 410));
+}
+// the layouts the decoder took before the generic output stage: luma 1x1, 2x1 or 2x2 with chroma 1x1 (3 components), R,G,B,A 1x1, greyscale.
+// They keep their own output kernels (planar_rgb_pack_kernel, yuv444p_to_uyvy_kernel, the planar 4:2:2 / 4:2:0 converters); the others go
+// through layout_pack_kernel.
+bool classic_layout(const Header &h)
+{
+        if (h.ncomp != 3) return true;
+        if (h.hs[1] != 1 || h.vs[1] != 1) return false;
+        if (h.hmax == 1 && h.vmax == 1) return true;
+        return !h.is_rgb() && h.hmax == 2 && h.vmax <= 2;
+}
+
 enum ParseMode {
         kHeadersOnly, // stop behind the first SOS header: everything a single-scan stream needs from the host
         kWalkScans,   // walk the entropy-coded data on the host to find where every scan ends and the next one starts (one scan per component)
@@ -141,7 +170,10 @@ int parse(const uint8_t *data, size_t len, Header &h, ParseMode mode)
                                 h.hs[c] = s[7 + 3 * c] >> 4;
                                 h.vs[c] = s[7 + 3 * c] & 15;
                                 h.tq[c] = s[8 + 3 * c];
-                                if (h.hs[c] < 1 || h.hs[c] > 2 || h.vs[c] < 1 || h.vs[c] > 2 || h.tq[c] > 3) return -1;
+                                // factors 1, 2 or 4: every ratio Hmax / H is then an integer (libjpeg refuses fractional ones); which combinations
+                                // are taken is decided behind the loop (layout_ok)
+                                const auto factor_ok = [](int f) { return f == 1 || f == 2 || f == 4; };
+                                if (!factor_ok(h.hs[c]) || !factor_ok(h.vs[c]) || h.tq[c] > 3) return -1;
                                 h.hmax = h.hs[c] > h.hmax ? h.hs[c] : h.hmax;
                                 h.vmax = h.vs[c] > h.vmax ? h.vs[c] : h.vmax;
                         }
@@ -194,6 +226,11 @@ int parse(const uint8_t *data, size_t len, Header &h, ParseMode mode)
                                 if (sc.comp[k] < 0 || sc.td[k] > 3 || sc.ta[k] > 3 || !h.dc[sc.td[k]].present || !h.ac[sc.ta[k]].present) return -1;
                         }
                         if (sc.ns != 1 && sc.ns != h.ncomp) return -1;
+                        if (sc.ns > 1) { // at most 10 blocks in an interleaved MCU (T.81 B.2.3; libjpeg: "Sampling factors too large for interleaved scan")
+                                int blocks = 0;
+                                for (int k = 0; k < sc.ns; k++) blocks += h.hs[sc.comp[k]] * h.vs[sc.comp[k]];
+                                if (blocks > kMaxMcuBlocks) return -1;
+                        }
                         sc.data_begin = pos + 2 + seglen;
                         if (mode == kHeadersOnly) {
                                 sc.data_end = len;
@@ -225,6 +262,7 @@ int parse(const uint8_t *data, size_t len, Header &h, ParseMode mode)
         if (h.ncomp == 4) { // R, G, B, alpha, each sampled 1x1 (what GPUJPEG's 4:4:4:4 writes); subsampled or Y'CbCr-K (Adobe transform 1, 2) four-component streams are not taken
                 if (h.adobe == 1 || h.adobe == 2 || h.hmax != 1 || h.vmax != 1) return -1;
         }
+        if (h.ncomp == 3 && !layout_ok(h)) return -1;
         return 0;
 }
 
@@ -1076,6 +1114,134 @@ __global__ void yuv444p_to_uyvy_kernel(const uint8_t *__restrict__ yp, const uin
         ((uint32_t *) (dst + (long) y * dpitch))[x] = u | (uint32_t) yp[o] << 8 | v << 16 | (uint32_t) yp[o + x1] << 24;
 }
 
+// ---- the output stage of the other sampling layouts (layout_ok: component 0 at the full resolution, components 1 and 2 at the ratio
+// 2^CX x 2^cy of it, CX 0..2, cy 0..1) -------------------------------------------------------------------------------------------------
+// Unpinned towards libgpujpeg, like every JPEG stage here (its own upsampling is not available); the rule is the one this decoder already
+// applies to 4:2:0 chroma lines and 4:2:2 chroma samples -- REPLICATION: a component sample covers its 2^CX x 2^cy pixels.  Then:
+//   R,G,B streams    -> UG_PF_RGB / UG_PF_RGBA: the pixel's R, G, B, as planar_rgb_pack_kernel packs them (RGBA: the shifts of decoder_t,
+//                       the byte they leave 0xFF; RGB: bytes R, G, B);
+//                    -> UG_PF_UYVY: vc_copylineRGBtoUYVY's arithmetic on the pixel pair (ToUYVY in pixfmt.hip), fused here;
+//   Y'CbCr streams   -> UG_PF_UYVY: the pair's chroma = (a + b) / 2 of its two pixels' samples, as yuv444p_to_uyvy_kernel -- which hands
+//                       4:2:2-like ratios (CX >= 1) their samples back unchanged; only 4:4:0 is averaged.
+// Odd widths: the last pair's second pixel is its first (yuv444p_to_uyvy_kernel's rule).  tests/jpeg_layout_restatement.py states it in numpy.
+// A lane takes 8 pixels of two rows: one 8-byte load per plane row, the chroma row once per row pair where both rows share it; the output
+// goes out in 16-byte stores where the destination allows it (8-byte for RGB's 24 bytes), 4-byte or single bytes elsewhere.
+enum LayoutOut { kLpRGB, kLpRGBA, kLpRGBtoUYVY, kLpYCCtoUYVY };
+struct LayoutPack {
+        const uint8_t *plane[3];
+        int ppitch[3];
+        int cy; // log2 of the chroma's vertical ratio
+        uint8_t *dst;
+        int dpitch, width, height, rs, gs, bs;
+};
+constexpr int kLpPx = 8, kLpWG = 256;
+
+// the samples of pixels x0 .. x0 + 7 of one row of a plane at horizontal ratio 2^SX: s[j] = the sample of pixel x0 + j -- one aligned 8-byte
+// load holds them all (x0 is a multiple of 8; the plane's pitch is a multiple of 8 and covers the component's width)
+template <int SX>
+__device__ __forceinline__ void lp_fetch(const uint8_t *__restrict__ row, int x0, uint32_t (&s)[kLpPx])
+{
+        const int c0 = x0 >> SX;
+        const uint2 q = *(const uint2 *) (row + (c0 & ~7));
+        const unsigned long long v = ((unsigned long long) q.y << 32 | q.x) >> (8 * (c0 & 7));
+#pragma unroll
+        for (int j = 0; j < kLpPx; j++) s[j] = (uint32_t) (v >> (8 * (j >> SX))) & 0xff;
+}
+
+// ToUYVY's Q14 arithmetic on one 8-bit R, G, B pixel (pixfmt.hip, vc_copylineToUYVY): Y', and the Cb, Cr sums a pair adds up
+__device__ __forceinline__ void lp_rgb_yuv(int r, int g, int b, int &y, int &u, int &v)
+{
+        y = ((r * 2992 + g * 10063 + b * 1016) >> 14) + 16;
+        u = r * -1649 + g * -5547 + b * 7196;
+        v = r * 7195 + g * -6536 + b * -659;
+}
+
+template <int OUT, int CX>
+__global__ __launch_bounds__(kLpWG) void layout_pack_kernel(LayoutPack p)
+{
+        const int x0 = (blockIdx.x * kLpWG + threadIdx.x) * kLpPx;
+        if (x0 >= p.width) return;
+        const int n = min(kLpPx, p.width - x0); // pixels of the 8 in the picture
+        constexpr int kBpp = OUT == kLpRGB ? 3 : (OUT == kLpRGBA ? 4 : 2);
+        constexpr int kWords = kLpPx * kBpp / 4;
+        uint32_t c1[kLpPx], c2[kLpPx];
+        for (int r = 0; r < 2; r++) {
+                const int y = 2 * blockIdx.y + r;
+                if (y >= p.height) break;
+                uint32_t c0[kLpPx];
+                lp_fetch<0>(p.plane[0] + (long) y * p.ppitch[0], x0, c0);
+                if (r == 0 || p.cy == 0) { // (a row pair starts at an even row: with cy = 1 both rows have the same chroma row)
+                        const int cyr = y >> p.cy;
+                        lp_fetch<CX>(p.plane[1] + (long) cyr * p.ppitch[1], x0, c1);
+                        lp_fetch<CX>(p.plane[2] + (long) cyr * p.ppitch[2], x0, c2);
+                }
+                uint32_t o[kWords];
+                if (OUT == kLpRGBA) {
+                        const uint32_t rest = 0xFFFFFFFFu ^ (0xFFu << p.rs) ^ (0xFFu << p.gs) ^ (0xFFu << p.bs);
+#pragma unroll
+                        for (int j = 0; j < kLpPx; j++) o[j] = rest | c0[j] << p.rs | c1[j] << p.gs | c2[j] << p.bs;
+                } else if (OUT == kLpRGB) {
+                        uint32_t px[kLpPx];
+#pragma unroll
+                        for (int j = 0; j < kLpPx; j++) px[j] = c0[j] | c1[j] << 8 | c2[j] << 16;
+#pragma unroll
+                        for (int i = 0; i < kWords; i++) { // bytes 4i .. 4i + 3 of 3 per pixel
+                                uint32_t v = 0;
+#pragma unroll
+                                for (int k = 0; k < 4; k++) v |= ((px[(4 * i + k) / 3] >> (8 * ((4 * i + k) % 3))) & 0xff) << (8 * k);
+                                o[i] = v;
+                        }
+                } else {
+#pragma unroll
+                        for (int i = 0; i < kLpPx / 2; i++) {
+                                const bool one = 2 * i + 1 >= n; // the last pair of an odd width: its second pixel is its first
+                                const int a = 2 * i, b = one ? 2 * i : 2 * i + 1;
+                                if (OUT == kLpYCCtoUYVY) {
+                                        const uint32_t u = (c1[a] + c1[b]) / 2, v = (c2[a] + c2[b]) / 2;
+                                        o[i] = u | c0[a] << 8 | v << 16 | c0[b] << 24;
+                                } else {
+                                        int y1, u1, v1, y2, u2, v2;
+                                        lp_rgb_yuv((int) c0[a], (int) c1[a], (int) c2[a], y1, u1, v1);
+                                        lp_rgb_yuv((int) c0[b], (int) c1[b], (int) c2[b], y2, u2, v2);
+                                        const int u = (((u1 + u2) / 2) >> 14) + 128, v = (((v1 + v2) / 2) >> 14) + 128; // C '/' truncates, '>>' floors (ToUYVY)
+                                        o[i] = (uint32_t) (u & 0xff) | (uint32_t) (y1 & 0xff) << 8 | (uint32_t) (v & 0xff) << 16 | (uint32_t) (y2 & 0xff) << 24;
+                                }
+                        }
+                }
+                uint8_t *d = p.dst + (long) y * p.dpitch + (long) x0 * kBpp;
+                const int bytes = OUT >= kLpRGBtoUYVY ? 4 * ((n + 1) / 2) : n * kBpp;
+                if (bytes == kWords * 4 && kWords % 4 == 0 && ((uintptr_t) d & 15) == 0) {
+#pragma unroll
+                        for (int i = 0; i < kWords / 4; i++) ((uint4 *) d)[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+                } else if (bytes == kWords * 4 && ((uintptr_t) d & 7) == 0) { // (RGB: 24 bytes a lane, every other lane 16-byte aligned)
+#pragma unroll
+                        for (int i = 0; i < kWords / 2; i++) ((uint2 *) d)[i] = make_uint2(o[2 * i], o[2 * i + 1]);
+                } else if (((uintptr_t) d & 3) == 0) {
+#pragma unroll
+                        for (int i = 0; i < kWords; i++) {
+                                if (4 * i + 4 <= bytes) ((uint32_t *) d)[i] = o[i];
+                                else if (4 * i < bytes) for (int k = 0; k < bytes - 4 * i; k++) d[4 * i + k] = (uint8_t) (o[i] >> (8 * k));
+                        }
+                } else {
+#pragma unroll
+                        for (int i = 0; i < kWords; i++) {
+#pragma unroll
+                                for (int k = 0; k < 4; k++) {
+                                        if (4 * i + k < bytes) d[4 * i + k] = (uint8_t) (o[i] >> (8 * k));
+                                }
+                        }
+                }
+        }
+}
+
+template <int OUT>
+void lp_launch(int cx, dim3 grid, hipStream_t st, const LayoutPack &lp)
+{
+        if (cx == 0) hipLaunchKernelGGL((layout_pack_kernel<OUT, 0>), grid, dim3(kLpWG), 0, st, lp);
+        else if (cx == 1) hipLaunchKernelGGL((layout_pack_kernel<OUT, 1>), grid, dim3(kLpWG), 0, st, lp);
+        else hipLaunchKernelGGL((layout_pack_kernel<OUT, 2>), grid, dim3(kLpWG), 0, st, lp);
+}
+
 struct Decoder {
         // device workspace, grown on demand
         uint8_t *stream = nullptr;
@@ -1170,7 +1336,7 @@ int ug_hip_jpeg_read_info(const void *jpeg_host, size_t len, int *width, int *he
         }
         if (width) *width = h.width;
         if (height) *height = h.height;
-        if (subsampling) *subsampling = h.ncomp == 1 ? 400 : (h.ncomp == 4 ? 4444 : (h.hs[0] == 2 ? (h.vs[0] == 2 ? 420 : 422) : 444));
+        if (subsampling) *subsampling = layout_code(h);
         if (is_rgb) *is_rgb = h.is_rgb();
         if (restart_interval) *restart_interval = h.ri;
         return UG_HIP_SUCCESS;
@@ -1213,12 +1379,7 @@ int ug_hip_jpeg_decoder_decode_sized(ug_hip_jpeg_decoder *dec, const void *jpeg_
                 ug::set_last_error_msg("ug_hip_jpeg_decoder_decode: the stream's picture size is not the size the destination was made for");
                 return UG_HIP_EINVAL;
         }
-        for (int c = 1; c < h.ncomp; c++) { // the sampling layouts the output stage knows: 4:4:4, 4:2:2, 4:2:0
-                if (h.hs[c] != 1 || h.vs[c] != 1) {
-                        ug::set_last_error_msg("ug_hip_jpeg_decoder_decode: unsupported sampling factors");
-                        return UG_HIP_EUNSUPP;
-                }
-        }
+        // (the sampling layouts were checked by parse(): every one it takes has an output path below)
         hipStream_t st = (hipStream_t) stream;
         // ---- workspace ----
         struct ScanPlan {
@@ -1445,11 +1606,38 @@ int ug_hip_jpeg_decoder_decode_sized(ug_hip_jpeg_decoder *dec, const void *jpeg_
         auto need_tmp = [&](ug_pixfmt_t f) {
                 return grow((void **) &d->tmp, &d->tmp_cap, (size_t) ug::linesize(f, w) * hh + 64);
         };
-        if (rgb) {
-                if (h.hs[0] != 1 || h.vs[0] != 1) {
-                        ug::set_last_error_msg("ug_hip_jpeg_decoder_decode: subsampled R,G,B streams are not supported");
+        if (!classic_layout(h)) { // the other sampling layouts: layout_pack_kernel
+                if (out != UG_PF_UYVY && out != UG_PF_RGB && out != UG_PF_RGBA) {
+                        ug::set_last_error_msg(out == UG_PF_I420 ? "ug_hip_jpeg_decoder_decode: I420 output needs a 4:2:0 stream" : "ug_hip_jpeg_decoder_decode: unsupported output codec");
                         return UG_HIP_EUNSUPP;
                 }
+                LayoutPack lp = {};
+                for (int c = 0; c < 3; c++) {
+                        lp.plane[c] = d->plane[c];
+                        lp.ppitch[c] = d->plane_pitch[c];
+                }
+                const int cx = h.hmax / h.hs[1] == 4 ? 2 : h.hmax / h.hs[1] - 1;
+                lp.cy = h.vmax / h.vs[1] - 1;
+                lp.width = w;
+                lp.height = hh;
+                lp.rs = rshift, lp.gs = gshift, lp.bs = bshift;
+                const int kind = rgb ? (out == UG_PF_RGB ? kLpRGB : (out == UG_PF_RGBA ? kLpRGBA : kLpRGBtoUYVY)) : kLpYCCtoUYVY;
+                const bool staged = kind == kLpYCCtoUYVY && out != UG_PF_UYVY; // Y'CbCr -> RGB / RGBA: through UYVY, as the other layouts
+                if (staged && !need_tmp(UG_PF_UYVY)) return UG_HIP_ERUNTIME;
+                lp.dst = staged ? d->tmp : (uint8_t *) dst_dev;
+                lp.dpitch = staged ? ug::linesize(UG_PF_UYVY, w) : dst_pitch;
+                const dim3 grid((unsigned) (((w + kLpPx - 1) / kLpPx + kLpWG - 1) / kLpWG), (unsigned) ((hh + 1) / 2));
+                switch (kind) {
+                case kLpRGB: lp_launch<kLpRGB>(cx, grid, st, lp); break;
+                case kLpRGBA: lp_launch<kLpRGBA>(cx, grid, st, lp); break;
+                case kLpRGBtoUYVY: lp_launch<kLpRGBtoUYVY>(cx, grid, st, lp); break;
+                default: lp_launch<kLpYCCtoUYVY>(cx, grid, st, lp); break;
+                }
+                UG_HIP_LAUNCH_CHECK();
+                if (!staged) return UG_HIP_SUCCESS;
+                return ug_hip_pixfmt_convert(UG_PF_UYVY, out, d->tmp, dst_dev, w, hh, lp.dpitch, dst_pitch, rshift, gshift, bshift, stream);
+        }
+        if (rgb) { // (4:4:4 here: subsampled R,G,B streams went to layout_pack_kernel)
                 if (out == UG_PF_RGB || out == UG_PF_RGBA) {
                         // the alpha of an R,G,B,A stream where the shifts leave it the top byte; elsewhere 0xFF (vc_copylineRGBtoRGBA)
                         const bool alpha = out == UG_PF_RGBA && h.ncomp == 4 && rshift == 0 && gshift == 8 && bshift == 16;

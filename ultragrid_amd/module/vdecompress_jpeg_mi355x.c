@@ -108,8 +108,20 @@ static decompress_status probe_internal_codec(unsigned char *buffer, size_t len,
         if (internal_prop != NULL) {
                 internal_prop->depth = 8;
                 internal_prop->rgb = rgb != 0;
-                // 4444: R, G, B + alpha (GPUJPEG_4444_U8_P0123, gpujpeg.c:255-259), reported RGB like the reference does
-                internal_prop->subsampling = sub == 4444 ? 4444 : (sub == 444 ? 4440 : (sub == 422 ? 4220 : (sub == 420 ? 4200 : 4000)));
+                // The table of gpujpeg.c:236-258 (GPUJPEG's pixel format -> the 4xxx code), R,G,B streams included (rgb = true with 4220 / 4200 for
+                // subsampled R,G,B, as the reference reports them):
+                //   444 -> 4440, 422 -> 4220, 420 -> 4200, 400 -> 4000, 4444 (R, G, B + alpha, GPUJPEG_4444_U8_P0123) -> 4444.
+                // Layouts GPUJPEG has no pixel format for go to the closest code that does not overstate the chroma:
+                //   440 (luma 1x2, chroma 1x1) -> 4440: every chroma column is there (decoded to UYVY with the pair's chroma averaged);
+                //   411 (4x1) -> 4220, 410 (4x2) -> 4200.
+                // Every code read_info gives has an entry: unlike gpujpeg.c:222,234 the probe never aborts.
+                switch (sub) {
+                case 4444: internal_prop->subsampling = 4444; break;
+                case 444: case 440: internal_prop->subsampling = 4440; break;
+                case 422: case 411: internal_prop->subsampling = 4220; break;
+                case 420: case 410: internal_prop->subsampling = 4200; break;
+                default: internal_prop->subsampling = 4000; break;
+                }
         }
         return DECODER_GOT_CODEC;
 }
