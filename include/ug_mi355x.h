@@ -473,6 +473,7 @@ int ug_hip_uyvy_to_jpeg42x_coeffs_batch(int subsampling, const void *src_dev, in
  * (gpujpeg.cpp:227-236,295-305,333-344):
  *   420: UG_PF_UYVY (line pairs averaged, uyvy_to_i420) or UG_PF_I420 (planes back to back, passthrough)   JFIF YCbCr
  *   422: UG_PF_UYVY (samples as they are, uyvy_to_i422)                                                     JFIF YCbCr
+ *   420 / 422 with UG_JPEG_INPUT_RGB (create_ex below): UG_PF_RGB, components R (2x2 / 2x1), G, B (1x1)       Adobe R,G,B
  *   444: UG_PF_RGB, components stay R, G, B (color_space_internal = GPUJPEG_RGB); written the libjpeg way for JCS_RGB:
  *        Adobe APP14 transform 0, component ids 'R','G','B', quantiser / Huffman table 0 for every component.
  * `encode` is synchronous on `stream` (it returns the stream length).  ug_hip_jpeg_encoder_max_size() is the capacity that can
@@ -496,17 +497,27 @@ int    ug_hip_jpeg_encoder_create_sub(int width, int height, int quality, int re
  *                limited range: RGB input + a Y'CbCr space -> a JFIF-shaped stream, components 1, 2, 3, chroma tables for Cb and Cr (Y601full IS
  *                JFIF); UYVY input + BT.601 (either range) -> the usual 4:2:x stream of the converted samples; UG_JPEG_CS_RGB with RGB input and
  *                UG_JPEG_CS_YCBCR_BT709 with UYVY / I420 input = UG_JPEG_CS_ASIS.  Not offered (UG_HIP_EUNSUPP): R, G, B components with
- *                subsampling 420 / 422, I420 with a conversion (ug_hip_yuv420p_to_uyvy first, as the module does), a Y'CbCr space or
- *                UG_JPEG_INPUT_UYVY with subsampling 4444 (no reader takes Y'CbCr + alpha; UYVY has none).  The colour stage is UNPINNED towards libgpujpeg like the FDCT: published BT.601 /
+ *                subsampling 420 / 422 without UG_JPEG_INPUT_RGB, UG_JPEG_INPUT_RGB with a Y'CbCr space, I420 with a conversion
+ *                (ug_hip_yuv420p_to_uyvy first, as the module does), a Y'CbCr space or UG_JPEG_INPUT_UYVY with subsampling 4444 (no reader takes Y'CbCr + alpha; UYVY has none).  The colour stage is UNPINNED towards libgpujpeg like the FDCT: published BT.601 /
  *                BT.709 definitions, fp32.
- *   flags        UG_JPEG_NONINTERLEAVED (subsampling 444 / 4444 only): one scan per component (T.81 A.2.2; restart intervals count blocks of the scan's
+ *   flags        UG_JPEG_NONINTERLEAVED (subsampling 444 / 4444, or 420 / 422 with UG_JPEG_INPUT_RGB): one scan per component (T.81 A.2.2; restart intervals count blocks of the scan's
  *                component) -- the reference's DEFAULT for RGB input (interleaved = 0 unless `:interleaved`, gpujpeg.cpp:303); the header then
  *                carries what those scans use (RGB: quantiser and Huffman table 0 only).  Three coder launches, each going on where the one before
  *                ended (one synchronisation, no intermediate buffer); the single interleaved scan is ONE fused kernel and faster.
  *                UG_JPEG_INPUT_UYVY (subsampling 444 only): the 4:4:4 encoder is fed UYVY instead of RGB (`-c jpeg:subsampling=444` on a 4:2:2
  *                source, gpujpeg.cpp:297-302 with GPUJPEG_422_U8_P1020 input): every pixel takes its pair's chroma, and the samples are coded as
  *                they are (UG_JPEG_CS_ASIS / _BT709: a Y'CbCr stream like the one RGB input + _BT709 gives), converted to BT.601 (either range),
- *                or converted to R, G, B (UG_JPEG_CS_RGB: the R,G,B stream of RGB input, from a 4:2:2 source). */
+ *                or converted to R, G, B (UG_JPEG_CS_RGB: the R,G,B stream of RGB input, from a 4:2:2 source).
+ *                UG_JPEG_INPUT_RGB (subsampling 420 / 422, internal_cs UG_JPEG_CS_ASIS or UG_JPEG_CS_RGB; the mirror of UG_JPEG_INPUT_UYVY): the 4:2:x
+ *                encoder is fed UG_PF_RGB (any pitch) and codes R, G, B components -- what the reference asks of GPUJPEG for RGB input with
+ *                `subsampling=420|422` (color_space_internal stays GPUJPEG_RGB, gpujpeg.cpp:295-305).  SOF0: 'R' sampled 2x2 (420) / 2x1 (422), 'G' and
+ *                'B' 1x1; quantiser and Huffman table 0 for every component, and only table 0 in the header; Adobe APP14 transform 0, no JFIF.
+ *                G and B are the box average of their 2x2 / 2x1 pixels, rounded half up, the last column / row taken again where a group runs
+ *                past the picture; blocks past a component plane replicate that plane's last sample.  With UG_JPEG_NONINTERLEAVED each scan covers
+ *                its component's own ceil(x / 8) x ceil(y / 8) blocks (T.81 A.2.2; the R scan: ceil(width / 8) x ceil(height / 8)), restart
+ *                intervals count them, and every scan starts again at RST0.  Encoding UYVY, I420 or RGBA with such an encoder: UG_HIP_EUNSUPP;
+ *                UG_JPEG_INPUT_RGB with subsampling 444 / 4444 or with UG_JPEG_INPUT_UYVY: UG_HIP_EINVAL.  The samples (the downsampling) are
+ *                UNPINNED towards libgpujpeg, like the FDCT: its preprocessor is not in the reference tree. */
 #define UG_JPEG_CS_ASIS                0
 #define UG_JPEG_CS_RGB                 1 /* GPUJPEG_RGB: full-range R'G'B' */
 #define UG_JPEG_CS_YCBCR_BT601         2 /* GPUJPEG_YCBCR_BT601: limited range (16-235 / 16-240) */
@@ -514,6 +525,7 @@ int    ug_hip_jpeg_encoder_create_sub(int width, int height, int quality, int re
 #define UG_JPEG_CS_YCBCR_BT709         4 /* GPUJPEG_YCBCR_BT709: limited range */
 #define UG_JPEG_NONINTERLEAVED         1
 #define UG_JPEG_INPUT_UYVY             2
+#define UG_JPEG_INPUT_RGB              4
 int    ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restart_interval, int subsampling, int internal_cs, int flags,
                                      ug_hip_jpeg_encoder **out);
 /* The colour stage by itself.  m[12]: out_i = m[4 i] * in_0 + m[4 i + 1] * in_1 + m[4 i + 2] * in_2 + m[4 i + 3] on 8-bit code values, cs_in -> cs_out

@@ -311,7 +311,9 @@ class JpegEncoder:
     """ug_hip_jpeg_encoder_* (gpujpeg_encoder_create / _encode / _destroy shape, gpujpeg.cpp:353,624,639)."""
 
     def __init__(self, w: int, h: int, quality: int = 75, restart_interval: int = 4, subsampling: int = 420, internal_cs: int = 0, flags: int = 0):
-        """internal_cs: L.JPEG_CS_* (color_space_internal of gpujpeg.cpp:303-305), flags: L.JPEG_NONINTERLEAVED, L.JPEG_INPUT_UYVY (ug_hip_jpeg_encoder_create_ex)"""
+        """internal_cs: L.JPEG_CS_* (color_space_internal of gpujpeg.cpp:303-305), flags: L.JPEG_NONINTERLEAVED, L.JPEG_INPUT_UYVY, L.JPEG_INPUT_RGB
+        (ug_hip_jpeg_encoder_create_ex).  subsampling=420 / 422 with L.JPEG_INPUT_RGB: an encoder of R, G, B components (R 2x2 / 2x1, G and B 1x1)
+        fed L.PF_RGB, in one interleaved scan or, with L.JPEG_NONINTERLEAVED, one scan per component."""
         import ctypes as C
         self._h = C.c_void_p()
         if internal_cs or flags:
@@ -324,7 +326,8 @@ class JpegEncoder:
         self._out = None
 
     def encode(self, src: torch.Tensor, in_fmt: int = L.PF_UYVY) -> bytes:
-        """src: UYVY (4:2:0 / 4:2:2 encoder), RGB (4:4:4 encoder), RGBA (4:4:4:4 encoder, subsampling=4444) or I420 planes back to back (4:2:0 encoder)."""
+        """src: UYVY (4:2:0 / 4:2:2 encoder), RGB (4:4:4 encoder, or a 4:2:x encoder created with L.JPEG_INPUT_RGB), RGBA (4:4:4:4 encoder,
+        subsampling=4444) or I420 planes back to back (4:2:0 encoder)."""
         import ctypes as C
         src = _u8(src)
         if self._out is None:

@@ -18,11 +18,14 @@
 #include "ug_common.h"
 #include "jpeg_fdct_device.h"
 
-// jpeg_fdct.hip: packed RGBA (4 B/px) -> R, G, B and A blocks (4:4:4:4), all with the divisors `div` -- declared here, its one caller, rather than in
+// jpeg_fdct.hip: packed RGBA (4 B/px) -> R, G, B and A blocks (4:4:4:4), packed RGB -> R, G, B blocks at 4:2:x -- declared here, their one caller, rather than in
 // ug_common.h, whose hash names the build that profiles/pmc_traffic.json's counters were taken on
 namespace ug {
 int jpeg_fdct_quant_rgba4444(const void *src, int pitch, int width, int height, int blocks_w, int blocks_h, const float *div,
                              int16_t *out_r, int16_t *out_g, int16_t *out_b, int16_t *out_a, ug_hip_stream_t stream);
+// packed RGB -> R (2 mcu_w x vs mcu_h blocks), G and B (box-averaged, mcu_w x mcu_h) of a 4:2:0 / 4:2:2 R, G, B stream; grid.z = frame
+int jpeg_fdct_quant_rgb42x(int sub, const void *src, int pitch, int width, int height, const float *div, int16_t *out_r, int16_t *out_g, int16_t *out_b,
+                           int frames, size_t src_stride, size_t r_bytes, size_t gb_bytes, ug_hip_stream_t stream);
 }
 
 namespace {
@@ -86,6 +89,7 @@ constexpr int kMaxBatch = 16; // frames per encode_batch call (the pinned length
 
 __global__ __launch_bounds__(256) void entropy_wave_kernel(const int16_t *__restrict__ cy, const int16_t *__restrict__ cb,
                                                            const int16_t *__restrict__ cr, const int16_t *__restrict__ ca /* nc = 3: the alpha plane */, int mcu_w, int n_mcu, int hs, int vs /* sampling factors of component 0: 2x2 (4:2:0), 2x1 (4:2:2), 1x1 (4:4:4) */,
+                                                           int gw0 /* blocks per row of component 0's grid: hs * mcu_w, or wider for a scan over a sub-rectangle of it */,
                                                            int ctab /* Huffman table set of components 1,2: 1 = chroma (YCbCr), 0 = same as component 0 (RGB) */,
                                                            int nc /* components behind component 0 in the MCU: 2 (3: R, G, B, A), or 0 for one scan of a non-interleaved stream (cy = that component) */,
                                                            int tab0 /* Huffman table set of component 0 */, int ri, int n_seg,
@@ -116,7 +120,7 @@ __global__ __launch_bounds__(256) void entropy_wave_kernel(const int16_t *__rest
         int mx = m0 % mcu_w, my = m0 / mcu_w, m = m0, b_next = 0;
         auto next_ptr = [&]() { // pointer of block (m, b_next), then advance
                 const int yrow = vs * my + (hs == 2 ? b_next >> 1 : 0), ycol = hs * mx + (hs == 2 ? b_next & 1 : 0); // block of component 0
-                const int16_t *p = b_next < ybl ? cy + 64 * ((long) yrow * (hs * mcu_w) + ycol)
+                const int16_t *p = b_next < ybl ? cy + 64 * ((long) yrow * gw0 + ycol)
                                                 : (b_next == ybl ? cb : (b_next == ybl + 1 ? cr : ca)) + 64L * m;
                 if (++b_next == per_mcu) {
                         b_next = 0;
@@ -563,6 +567,9 @@ struct CodeArgs {
         // SRC = 0 only: nc = chroma blocks of an MCU -- 2 (3: R, G, B, A, the fourth plane in ca), or 0 for the scan of ONE component (a non-interleaved scan, T.81 A.2.2: its MCU is one block, cy = that
         // component's blocks); tab0 = the Huffman table pair of the blocks b < hs * vs (0; 1 for the Cb / Cr scans of a non-interleaved YCbCr stream)
         int nc, tab0;
+        // SRC = 0: blocks per row of component 0's grid -- hs * mcu_w, or wider when the scan walks a sub-rectangle of it (the R scan of a non-interleaved
+        // 4:2:x R, G, B stream: ceil(width / 8) x ceil(height / 8) blocks of the MCU-padded grid, T.81 A.2.2)
+        int gw0;
         // SRC = 0, one-launch placement only: the stream of frame f goes on at byte base[f] - 2 of its buffer -- behind the previous scan of a non-interleaved stream,
         // over the EOI that scan ended with (NULL: at byte 0).  The word is the length the previous scan's launch left in (mapped, pinned) host memory: kernels of one
         // stream run in order, so it is final when this launch reads it.
@@ -718,7 +725,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SRC 
                 const int m = m_first + ml;
                 const int my = m / a.mcu_w, mx = m - my * a.mcu_w;
                 const int yrow = a.vs * my + (a.hs == 2 ? b >> 1 : 0), ycol = a.hs * mx + (a.hs == 2 ? b & 1 : 0);
-                const int16_t *p = b < ybl ? cy + 64 * ((long) yrow * (a.hs * a.mcu_w) + ycol) : (b == ybl ? cb : (b == ybl + 1 ? cr : ca)) + 64L * m;
+                const int16_t *p = b < ybl ? cy + 64 * ((long) yrow * a.gw0 + ycol) : (b == ybl ? cb : (b == ybl + 1 ? cr : ca)) + 64L * m;
                 if (!active) p = cy;
                 // A block is one 128-byte line.  If every lane fetched its own block 16 bytes at a time, each of the 8 load
                 // instructions of the wave would touch 64 different lines and use an eighth of each: 8x the traffic between L2 and
@@ -1370,6 +1377,7 @@ __global__ __launch_bounds__(256) void compact_kernel(const uint8_t *__restrict_
 struct NoriScan {
         const int16_t *c0, *c1, *c2, *c3; // component 0 (hs x vs blocks per MCU), the components behind it (nc = 2; 3: R, G, B, A) -- or one component alone (nc = 0: a scan of a non-interleaved stream)
         int mcu_w, n_mcu, hs, vs, nc, tab0, ctab;
+        int gw0; // blocks per row of component 0's grid (hs * mcu_w; a scan over a sub-rectangle of a wider grid: that grid's width)
         int ri; // MCUs per restart interval (the predictions start from 0 there); n_mcu: none
 };
 
@@ -1381,7 +1389,7 @@ __device__ __forceinline__ const int16_t *nori_block(const NoriScan &s, uint32_t
         auto luma = [&](int mm, int jj) {
                 const int my = mm / s.mcu_w, mx = mm - my * s.mcu_w;
                 const int yrow = s.vs * my + (s.hs == 2 ? jj >> 1 : 0), ycol = s.hs * mx + (s.hs == 2 ? jj & 1 : 0);
-                return s.c0 + 64 * ((long) yrow * (s.hs * s.mcu_w) + ycol);
+                return s.c0 + 64 * ((long) yrow * s.gw0 + ycol);
         };
         if (j < ybl) {
                 tab = s.tab0;
@@ -1673,6 +1681,12 @@ struct Encoder {
         int nc;        // components behind component 0 in an MCU: 2, or 3 with alpha
         std::vector<uint8_t> scan_header[4]; // non-interleaved: what precedes the entropy-coded bytes of scan c (scan 0: the whole header)
         uint8_t *scan_header_dev[4];
+        // UG_JPEG_INPUT_RGB: a 4:2:x encoder fed RGB that codes R, G, B components -- R sampled hs x vs over cy's grid, G and B 1x1 (box-averaged) over
+        // cb / cr's; table 0 for all three (gpujpeg.cpp:303-305 keeps color_space_internal = GPUJPEG_RGB at any subsampling)
+        bool rgb_sub;
+        // non-interleaved: the blocks of scan c -- scan_bw[c] x (scan_n[c] / scan_bw[c]) of a grid scan_gw[c] blocks wide (T.81 A.2.2: ceil(x_c / 8) x
+        // ceil(y_c / 8); the R scan of a 4:2:x R, G, B stream covers less than its MCU-padded grid), in scan_nseg[c] segments; n_seg is the largest of these
+        int scan_bw[4], scan_n[4], scan_gw[4], scan_nseg[4];
 };
 constexpr int kTotalWords = 32; // per block of total_host: kMaxBatch lengths, [kMaxBatch] "a wait was given up", [kMaxBatch + 1] "a slot overflowed"
 // total_host: the call's block, one per scan of a non-interleaved stream (up to four), one for odd words
@@ -1686,10 +1700,12 @@ void put16(std::vector<uint8_t> &v, int x) { v.push_back((uint8_t) (x >> 8)); v.
 // quantiser / Huffman table 0.  4:4:4, ycc: JFIF again, components 1, 2, 3 at 1x1.  scan >= 0: the header of a NON-INTERLEAVED stream up to and
 // including the SOS of its first scan (scan = 0; an R, G, B stream then carries table 0 only, the layout of tests/jpeg_bitstream.py
 // write_jpeg_noninterleaved), or just the SOS segment of scan 1 / 2 (/ 3).  alpha: the R, G, B stream with a fourth component 'A' behind them, sampled
-// 1x1, tables 0 like the others (4:4:4:4).
-std::vector<uint8_t> build_header(int w, int h, const uint8_t *ql, const uint8_t *qc, int ri, int sub, bool ycc = false, int scan = -1, bool alpha = false)
+// 1x1, tables 0 like the others (4:4:4:4).  rgb_sub: the R, G, B stream of a 4:2:0 / 4:2:2 encoder (R sampled 2x2 / 2x1, G and B 1x1), table 0 only in
+// either scan layout (tests/jpeg_layout_bitstream.py write_layout_jpeg, rgb = "both").
+std::vector<uint8_t> build_header(int w, int h, const uint8_t *ql, const uint8_t *qc, int ri, int sub, bool ycc = false, int scan = -1, bool alpha = false,
+                                  bool rgb_sub = false)
 {
-        const bool rgb = sub == 444 && !ycc;
+        const bool rgb = (sub == 444 && !ycc) || rgb_sub;
         const uint8_t id[4] = { (uint8_t) (rgb ? 'R' : 1), (uint8_t) (rgb ? 'G' : 2), (uint8_t) (rgb ? 'B' : 3), 'A' };
         const uint8_t t12 = rgb ? 0 : 1;
         std::vector<uint8_t> v;
@@ -1703,7 +1719,7 @@ std::vector<uint8_t> build_header(int w, int h, const uint8_t *ql, const uint8_t
         } else {
                 v.insert(v.end(), { 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0 });
         }
-        const bool table0_only = scan == 0 && rgb;
+        const bool table0_only = rgb && (scan == 0 || rgb_sub); // (the interleaved 4:4:4 R, G, B header keeps its unused table 1)
         for (int t = 0; t < (table0_only ? 1 : 2); t++) {
                 v.insert(v.end(), { 0xFF, 0xDB, 0, 67, (uint8_t) t });
                 for (int i = 0; i < 64; i++) v.push_back((t ? qc : ql)[kZigHost[i]]);
@@ -1849,9 +1865,19 @@ int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restar
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create: subsampling must be 420, 422, 444 or 4444");
                 return UG_HIP_EUNSUPP;
         }
-        if (internal_cs < UG_JPEG_CS_ASIS || internal_cs > UG_JPEG_CS_YCBCR_BT709 || (flags & ~(UG_JPEG_NONINTERLEAVED | UG_JPEG_INPUT_UYVY))) {
+        if (internal_cs < UG_JPEG_CS_ASIS || internal_cs > UG_JPEG_CS_YCBCR_BT709 || (flags & ~(UG_JPEG_NONINTERLEAVED | UG_JPEG_INPUT_UYVY | UG_JPEG_INPUT_RGB))) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create_ex: unknown colour space or flag");
                 return UG_HIP_EINVAL;
+        }
+        // UG_JPEG_INPUT_RGB: the mirror of UG_JPEG_INPUT_UYVY -- a 4:2:x encoder fed RGB, the samples coded as R, G, B (a 4:4:4 encoder takes RGB anyway)
+        const bool rgb_sub = (flags & UG_JPEG_INPUT_RGB) != 0;
+        if (rgb_sub && (subsampling == 444 || subsampling == 4444 || (flags & UG_JPEG_INPUT_UYVY))) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_create_ex: UG_JPEG_INPUT_RGB is for a 4:2:0 / 4:2:2 encoder, and excludes UG_JPEG_INPUT_UYVY");
+                return UG_HIP_EINVAL;
+        }
+        if (rgb_sub && internal_cs != UG_JPEG_CS_ASIS && internal_cs != UG_JPEG_CS_RGB) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_create_ex: UG_JPEG_INPUT_RGB codes R, G, B components (Y'CbCr from RGB at 4:2:x is not offered)");
+                return UG_HIP_EUNSUPP;
         }
         // 4:4:4:4 = R, G, B + alpha from RGBA input: no reader takes Y'CbCr + alpha, and UYVY carries no alpha
         const bool alpha = subsampling == 4444;
@@ -1860,9 +1886,9 @@ int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restar
                 return UG_HIP_EUNSUPP;
         }
         if (alpha) subsampling = 444; // the R, G, B stream of the same options, a fourth component behind
-        if (subsampling != 444 && ((flags & (UG_JPEG_NONINTERLEAVED | UG_JPEG_INPUT_UYVY)) || internal_cs == UG_JPEG_CS_RGB)) {
+        if (subsampling != 444 && !rgb_sub && ((flags & (UG_JPEG_NONINTERLEAVED | UG_JPEG_INPUT_UYVY)) || internal_cs == UG_JPEG_CS_RGB)) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create_ex: a 4:2:x stream is Y'CbCr in one interleaved scan (R, G, B components, one scan per component, "
-                                       "UG_JPEG_INPUT_UYVY: 4:4:4)");
+                                       "UG_JPEG_INPUT_UYVY: 4:4:4; R, G, B at 4:2:x: UG_JPEG_INPUT_RGB)");
                 return UG_HIP_EUNSUPP;
         }
         Encoder *e = new Encoder();
@@ -1874,7 +1900,8 @@ int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restar
         e->ycc = subsampling == 444 && (internal_cs >= UG_JPEG_CS_YCBCR_BT601 || (e->in_uyvy && internal_cs == UG_JPEG_CS_ASIS));
         e->cs_rgb = e->ycc && !e->in_uyvy ? internal_cs : 0;
         e->cs_uyvy = subsampling != 444 && (internal_cs == UG_JPEG_CS_YCBCR_BT601 || internal_cs == UG_JPEG_CS_YCBCR_BT601_256LVLS) ? internal_cs : 0;
-        e->ctab = subsampling == 444 && !e->ycc ? 0 : 1;
+        e->rgb_sub = rgb_sub;
+        e->ctab = (subsampling == 444 && !e->ycc) || rgb_sub ? 0 : 1;
         e->width = width; e->height = height; e->quality = quality;
         e->force_wave_kernel = getenv("UG_JPEG_WAVE_KERNEL") != nullptr && getenv("UG_JPEG_WAVE_KERNEL")[0] == '1';
         e->allow_fused = !(getenv("UG_JPEG_FUSED") != nullptr && getenv("UG_JPEG_FUSED")[0] == '0');
@@ -1889,22 +1916,36 @@ int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restar
         // header -- coded by a single wave, block after block (entropy_wave_kernel): milliseconds per frame instead of microseconds; for streams a reader without
         // restart marker support must take
         e->ri = restart_interval ? restart_interval : e->n_mcu;
-        if ((long) e->ri * (e->ybl + e->nc) * kRawBytesPerBlock + 8 > (1L << 30)) {
+        // the blocks of every scan of a non-interleaved stream: component c's own ceil(x_c / 8) x ceil(y_c / 8) (T.81 A.2.2) -- the MCU grid, but for the
+        // R scan of a 4:2:x R, G, B stream, which walks ceil(width / 8) x ceil(height / 8) blocks of its 2 mcu_w x vs mcu_h grid
+        for (int c = 0; c < 4; c++) {
+                const bool sub0 = c == 0 && rgb_sub;
+                e->scan_bw[c] = sub0 ? (width + 7) / 8 : e->mcu_w;
+                e->scan_n[c] = sub0 ? e->scan_bw[c] * ((height + 7) / 8) : e->n_mcu;
+                e->scan_gw[c] = sub0 ? e->hs * e->mcu_w : e->mcu_w;
+        }
+        // one component per scan of a 4:2:x R, G, B stream: restart 0 = one segment of the largest scan's blocks; a segment holds ri blocks of one component
+        const bool nonint_sub = e->nonint && rgb_sub;
+        if (nonint_sub && !restart_interval) e->ri = e->scan_n[0];
+        const int seg_blocks = nonint_sub ? 1 : e->ybl + e->nc; // blocks per unit of the restart interval, at most
+        if ((long) e->ri * seg_blocks * kRawBytesPerBlock + 8 > (1L << 30)) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create: picture too large for a scan without restart intervals");
                 delete e;
                 return UG_HIP_EUNSUPP;
         }
         e->n_seg = (e->n_mcu + e->ri - 1) / e->ri;
-        e->cap = e->ri * (e->ybl + e->nc) * kRawBytesPerBlock + 8; // unstuffed scan bytes of one segment (worst case 27 bits per coefficient)
+        for (int c = 0; c < 4; c++) e->scan_nseg[c] = (e->scan_n[c] + e->ri - 1) / e->ri;
+        if (nonint_sub) e->n_seg = e->scan_nseg[0]; // (the largest scan: what the per-segment buffers are sized for)
+        e->cap = e->ri * seg_blocks * kRawBytesPerBlock + 8; // unstuffed scan bytes of one segment (worst case 27 bits per coefficient)
         uint8_t ql[64], qc[64];
         float div[128];
         ug_hip_jpeg_qtable(quality, 0, ql);
         ug_hip_jpeg_qtable(quality, 1, qc);
         ug_hip_jpeg_divisors(ql, div);
         ug_hip_jpeg_divisors(e->ctab == 0 ? ql : qc, div + 64); // R, G, B: every component is quantised with table 0
-        e->header = build_header(width, height, ql, qc, restart_interval, e->sub, e->ycc, -1, e->alpha);
+        e->header = build_header(width, height, ql, qc, restart_interval, e->sub, e->ycc, -1, e->alpha, rgb_sub);
         if (e->nonint) {
-                for (int c = 0; c < 1 + e->nc; c++) e->scan_header[c] = build_header(width, height, ql, qc, restart_interval, e->sub, e->ycc, c, e->alpha);
+                for (int c = 0; c < 1 + e->nc; c++) e->scan_header[c] = build_header(width, height, ql, qc, restart_interval, e->sub, e->ycc, c, e->alpha, rgb_sub);
                 e->header = e->scan_header[0]; // (what max_size and the capacity check count)
         }
         hipError_t err = hipSuccess;
@@ -1954,6 +1995,11 @@ void ug_hip_jpeg_encoder_destroy(ug_hip_jpeg_encoder *enc) { destroy((Encoder *)
 size_t ug_hip_jpeg_encoder_max_size(const ug_hip_jpeg_encoder *enc)
 {
         const Encoder *e = (const Encoder *) enc;
+        if (e && e->nonint && e->rgb_sub) { // every scan's segments (cap: ri blocks of one component), every byte stuffed, + the SOS of scans 1 and 2
+                size_t segs = 0;
+                for (int c = 0; c < 3; c++) segs += (size_t) e->scan_nseg[c];
+                return e->header.size() + 20 + segs * (2 * (size_t) e->cap + 2);
+        }
         // every byte stuffed = worst case (+ the SOS of two more scans; three with alpha)
         return e ? e->header.size() + (e->alpha ? 30 : 20) + (size_t) e->n_seg * (2 * (size_t) e->cap + 2) : 0;
 }
@@ -2021,6 +2067,10 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:4:4:4 encoder takes RGBA, and only it takes RGBA");
                 return UG_HIP_EUNSUPP;
         }
+        if (e->rgb_sub && in != UG_PF_RGB) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:2:x encoder created with UG_JPEG_INPUT_RGB takes RGB only");
+                return UG_HIP_EUNSUPP;
+        }
         // ---- a 4:4:4 encoder fed UYVY (UG_JPEG_INPUT_UYVY): the frame(s) as 3 B/px in the coded colour space, which then take the place of RGB input ----
         if (e->sub == 444 && !e->alpha && e->in_uyvy != (in == UG_PF_UYVY)) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:4:4 encoder takes RGB, or UYVY when created with UG_JPEG_INPUT_UYVY");
@@ -2062,6 +2112,10 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
         } else if (in == UG_PF_UYVY && e->sub != 444) { // fused unpack + subsample + FDCT + quantise, grid.z = frame
                 rc = ug_hip_uyvy_to_jpeg42x_coeffs_batch(e->sub, src_dev, src_pitch, w, h, e->div, e->cy, e->cb, e->cr, frames, src_stride,
                                                          (size_t) bs.coef_y * 2, (size_t) bs.coef_c * 2, stream);
+        } else if (in == UG_PF_RGB && e->rgb_sub) { // R, G, B at 4:2:x: R over its full grid, G and B box-averaged, in one pass over the frame(s) (rgb_jpeg42x_kernel)
+                if (!src_pitch) src_pitch = 3 * w;
+                rc = ug::jpeg_fdct_quant_rgb42x(e->sub, src_dev, src_pitch, w, h, e->div, e->cy, e->cb, e->cr, frames, src_stride, (size_t) bs.coef_y * 2,
+                                                (size_t) bs.coef_c * 2, stream);
         } else if (in == UG_PF_RGB && e->sub == 444) { // GPUJPEG_444_U8_P012, components kept as R, G, B (gpujpeg.cpp:303-305,336)
                 if (!src_pitch) src_pitch = 3 * w;
                 for (int f = 0; f < frames && rc == UG_HIP_SUCCESS; f++) {
@@ -2103,7 +2157,11 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
         // the block-parallel coder, fused or behind the front end; two_launch: slots + gather launch, else the one-launch placement (look-back)
         // `scan` = nullptr: the frame's one interleaved scan.  Else one scan of a non-interleaved stream: a single component's blocks (its MCU is one block),
         // its own header bytes, destination and length words; always the one-launch placement
-        struct ScanPlan { const int16_t *coef; int tab0; const uint8_t *header; int header_len; const uint32_t *base; uint32_t *total; };
+        struct ScanPlan {
+                const int16_t *coef; int tab0; const uint8_t *header; int header_len; const uint32_t *base; uint32_t *total;
+                int bw, n, gw, n_seg; // the scan's blocks: bw x (n / bw) of a grid gw blocks wide, in n_seg segments (Encoder::scan_*)
+                long stride;          // int16 elements between the frames' planes of the component
+        };
         auto launch_coder = [&](bool two_launch, const ScanPlan *scan = nullptr) -> int {
                 const int S = scan ? e->ri : S_frame;
                 const bool fused = !scan && (fused_yuv || fused_rgb || fused_i420); // (shadows the call's: a scan of one component reads coefficients)
@@ -2113,8 +2171,12 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 }
                 CodeArgs a = {};
                 a.mcu_w = e->mcu_w; a.n_mcu = e->n_mcu; a.hs = e->hs; a.vs = e->vs; a.ctab = e->ctab; a.ri = e->ri; a.n_seg = e->n_seg; a.S = S;
+                a.gw0 = e->hs * e->mcu_w;
+                if (scan) { // a scan of one component: its MCU is one block
+                        a.mcu_w = scan->bw; a.n_mcu = scan->n; a.hs = a.vs = 1; a.n_seg = scan->n_seg; a.gw0 = scan->gw;
+                }
                 a.nc = scan ? 0 : e->nc; a.tab0 = scan ? scan->tab0 : 0;
-                a.cy = scan ? scan->coef : e->cy; a.cb = e->cb; a.cr = e->cr; a.ca = e->ca; a.coef_y = bs.coef_y; a.coef_c = bs.coef_c;
+                a.cy = scan ? scan->coef : e->cy; a.cb = e->cb; a.cr = e->cr; a.ca = e->ca; a.coef_y = scan ? scan->stride : bs.coef_y; a.coef_c = bs.coef_c;
                 a.src = (const uint8_t *) src_dev; a.pitch = src_pitch; a.width = w; a.height = h; a.src_stride = src_stride;
                 a.out = (uint8_t *) out_dev; a.out_stride = out_stride; a.capacity = out_capacity; a.header = e->header_dev; a.header_len = (int) e->header.size();
                 a.total_pinned = e->total_host_dev;
@@ -2126,7 +2188,7 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 a.flat = 0; // decided below, once the number of workgroups of a frame is known
                 // divisions by S, blocks per MCU and MCUs per row as multiplications, where the ranges allow (CodeArgs)
                 {
-                        const int per_mcu = e->hs * e->vs + a.nc;
+                        const int per_mcu = a.hs * a.vs + a.nc;
                         auto m16 = [](int d) { return (uint32_t) (65536 / d + 1); };
                         auto m32 = [](long d) { return d > 1 ? (uint32_t) ((1ull << 32) / (unsigned long long) d + 1ull) : 0u; };
                         a.S_m16 = m16(S);             // x < 256 lanes, S <= 256: x * S < 2^16
@@ -2151,7 +2213,11 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                         // (the kernel's per-segment LDS words are sized for segments of at least 3 blocks, kMaxSeg = lanes / 3 + 1: the shortest ones an
                         // interleaved scan has; a one-component scan with restart interval 1 or 2 has shorter ones and leaves lanes idle instead)
                         a.G = std::min(64 * waves / S, 64 * waves / 3);
-                        a.n_wg = (e->n_seg + a.G - 1) / a.G;
+                        a.n_wg = (a.n_seg + a.G - 1) / a.G;
+                }
+                if (a.n_wg > e->n_mcu) { // (the look-back's status words and the workgroups' byte counts: n_mcu per frame; a workgroup codes at least 21 blocks)
+                        ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: more coder workgroups than status words");
+                        return UG_HIP_ERUNTIME;
                 }
                 if (two_launch) {
                         // a slot holds whatever the one-pass path can produce: every window full, every byte stuffed, the markers (+ the padding the
@@ -2210,13 +2276,15 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
         static const bool nori_off = getenv("UG_JPEG_NORI") != nullptr && getenv("UG_JPEG_NORI")[0] == '0';
         const bool nori = wave_path && !e->force_wave_kernel && e->n_seg == 1 && !nori_off && (unsigned long long) e->cap * 8ull < (1ull << 32); // (UG_JPEG_WAVE_KERNEL=1: the old kernels throughout)
         auto code_without_restart = [&](const ScanPlan *scan) -> int {
-                const uint32_t n_blocks = (uint32_t) e->n_mcu * (uint32_t) (scan ? 1 : e->ybl + e->nc);
+                const uint32_t n_blocks = scan ? (uint32_t) scan->n : (uint32_t) e->n_mcu * (uint32_t) (e->ybl + e->nc);
+                // (a bit count per block of the largest scan + the total: the R scan of a 4:2:x R, G, B stream has at most ybl * n_mcu blocks)
                 if (!e->nori_bits) UG_HIP_TRY(hipMalloc((void **) &e->nori_bits, ((size_t) e->n_mcu * (e->ybl + e->nc) + 1) * 4));
                 for (int f = 0; f < frames; f++) {
                         NoriScan s = {};
-                        s.c0 = (scan ? scan->coef : e->cy) + f * bs.coef_y; s.c1 = e->cb + f * bs.coef_c; s.c2 = e->cr + f * bs.coef_c;
+                        s.c0 = scan ? scan->coef + f * scan->stride : e->cy + f * bs.coef_y; s.c1 = e->cb + f * bs.coef_c; s.c2 = e->cr + f * bs.coef_c;
                         s.c3 = e->ca ? e->ca + f * bs.coef_c : nullptr;
-                        s.mcu_w = e->mcu_w; s.n_mcu = e->n_mcu; s.hs = scan ? 1 : e->hs; s.vs = scan ? 1 : e->vs; s.nc = scan ? 0 : e->nc; s.tab0 = scan ? scan->tab0 : 0; s.ctab = e->ctab; s.ri = e->n_mcu;
+                        s.mcu_w = scan ? scan->bw : e->mcu_w; s.n_mcu = scan ? scan->n : e->n_mcu; s.hs = scan ? 1 : e->hs; s.vs = scan ? 1 : e->vs; s.nc = scan ? 0 : e->nc;
+                        s.tab0 = scan ? scan->tab0 : 0; s.ctab = e->ctab; s.ri = s.n_mcu; s.gw0 = scan ? scan->gw : e->hs * e->mcu_w;
                         hipLaunchKernelGGL(nori_len_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, e->nori_bits);
                         hipLaunchKernelGGL(nori_scan_kernel, dim3(1), dim3(1024), 0, st, e->nori_bits, n_blocks);
                         uint32_t *const bits_host = e->total_host + kOddBlock * kTotalWords; // (a word of the pinned block of its own)
@@ -2249,7 +2317,8 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
         const bool seg_parallel = wave_path && !e->force_wave_kernel && e->n_seg > 1 && !nori_off &&
                                   0.9 * (double) e->ri * (e->nonint ? 1 : e->ybl + e->nc) > 150.0 + 5.2e-5 * (double) w * (double) h;
         auto fill_segments = [&](const ScanPlan *scan) -> int {
-                const uint32_t per_mcu = (uint32_t) (scan ? 1 : e->ybl + e->nc), n_blocks = (uint32_t) e->n_mcu * per_mcu;
+                const uint32_t per_mcu = (uint32_t) (scan ? 1 : e->ybl + e->nc), n_blocks = scan ? (uint32_t) scan->n : (uint32_t) e->n_mcu * per_mcu;
+                const int n_seg = scan ? scan->n_seg : e->n_seg;
                 if (!e->nori_bits) UG_HIP_TRY(hipMalloc((void **) &e->nori_bits, ((size_t) e->n_mcu * (e->ybl + e->nc) + 1) * 4));
                 if (e->nori_ff_cap < (size_t) e->n_seg + 1) {
                         if (e->nori_ff) (void) hipFree(e->nori_ff);
@@ -2260,16 +2329,17 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 }
                 for (int f = 0; f < frames; f++) {
                         NoriScan s = {};
-                        s.c0 = (scan ? scan->coef : e->cy) + f * bs.coef_y; s.c1 = e->cb + f * bs.coef_c; s.c2 = e->cr + f * bs.coef_c;
+                        s.c0 = scan ? scan->coef + f * scan->stride : e->cy + f * bs.coef_y; s.c1 = e->cb + f * bs.coef_c; s.c2 = e->cr + f * bs.coef_c;
                         s.c3 = e->ca ? e->ca + f * bs.coef_c : nullptr;
-                        s.mcu_w = e->mcu_w; s.n_mcu = e->n_mcu; s.hs = scan ? 1 : e->hs; s.vs = scan ? 1 : e->vs; s.nc = scan ? 0 : e->nc; s.tab0 = scan ? scan->tab0 : 0; s.ctab = e->ctab; s.ri = e->ri;
+                        s.mcu_w = scan ? scan->bw : e->mcu_w; s.n_mcu = scan ? scan->n : e->n_mcu; s.hs = scan ? 1 : e->hs; s.vs = scan ? 1 : e->vs; s.nc = scan ? 0 : e->nc;
+                        s.tab0 = scan ? scan->tab0 : 0; s.ctab = e->ctab; s.ri = e->ri; s.gw0 = scan ? scan->gw : e->hs * e->mcu_w;
                         uint32_t *const raw = e->scratch + (size_t) f * bs.raw_words;
                         hipLaunchKernelGGL(nori_len_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, e->nori_bits);
                         hipLaunchKernelGGL(nori_segscan_kernel, dim3(1), dim3(1024), 0, st, e->nori_bits, n_blocks, (uint32_t) e->ri * per_mcu, e->nori_ff);
-                        UG_HIP_TRY(hipMemsetAsync(raw, 0, (size_t) e->n_seg * (size_t) e->cap, st));
+                        UG_HIP_TRY(hipMemsetAsync(raw, 0, (size_t) n_seg * (size_t) e->cap, st));
                         hipLaunchKernelGGL(nori_emit_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, (const uint32_t *) e->nori_bits, raw, (uint32_t) e->ri * per_mcu,
                                            (uint32_t) (e->cap / 4));
-                        hipLaunchKernelGGL(nori_segstat_kernel, dim3((e->n_seg + 3) / 4), dim3(256), 0, st, (const uint32_t *) raw, (uint32_t) (e->cap / 4), (const uint32_t *) e->nori_ff, e->n_seg,
+                        hipLaunchKernelGGL(nori_segstat_kernel, dim3((n_seg + 3) / 4), dim3(256), 0, st, (const uint32_t *) raw, (uint32_t) (e->cap / 4), (const uint32_t *) e->nori_ff, n_seg,
                                            e->seg_len + (size_t) f * bs.seg, e->seg_ff + (size_t) f * bs.seg, e->chunk_tot + (size_t) f * bs.tot_words);
                 }
                 return UG_HIP_SUCCESS;
@@ -2293,7 +2363,8 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 for (int c = 0; c < n_scans; c++) {
                         const int16_t *const planes[4] = { e->cy, e->cb, e->cr, e->ca };
                         const ScanPlan pl = { planes[c], e->ycc && c > 0 ? 1 : 0, e->scan_header_dev[c], (int) e->scan_header[c].size(),
-                                              c > 0 ? e->total_host_dev + c * kTotalWords : nullptr, e->total_host_dev + (c + 1) * kTotalWords };
+                                              c > 0 ? e->total_host_dev + c * kTotalWords : nullptr, e->total_host_dev + (c + 1) * kTotalWords,
+                                              e->scan_bw[c], e->scan_n[c], e->scan_gw[c], e->scan_nseg[c], c > 0 ? bs.coef_c : bs.coef_y };
                         if (nori) {
                                 const int nrc = code_without_restart(&pl);
                                 if (nrc != UG_HIP_SUCCESS) return nrc;
@@ -2301,15 +2372,17 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                         }
                         if (wave_path) { // restart intervals of more than 256 blocks: a wave per segment, then the compaction -- scan after scan on the stream
                                 UG_HIP_TRY(hipMemsetAsync(e->chunk_tot, 0, (size_t) bs.tot_words * 4 * frames, st));
+                                BatchStride bsc = bs; // (the frames' planes of this scan's component)
+                                bsc.coef_y = pl.stride;
                                 if (seg_parallel) {
                                         const int frc = fill_segments(&pl);
                                         if (frc != UG_HIP_SUCCESS) return frc;
                                 } else {
-                                        hipLaunchKernelGGL(entropy_wave_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, pl.coef, pl.coef, pl.coef, pl.coef, e->mcu_w, e->n_mcu, 1, 1,
-                                                           0, 0, pl.tab0, e->ri, e->n_seg, e->scratch, e->cap / 4, e->seg_len, e->seg_ff, e->chunk_tot, bs);
+                                        hipLaunchKernelGGL(entropy_wave_kernel, dim3((pl.n_seg + 3) / 4, frames), dim3(256), 0, st, pl.coef, pl.coef, pl.coef, pl.coef, pl.bw, pl.n, 1, 1,
+                                                           pl.gw, 0, 0, pl.tab0, e->ri, pl.n_seg, e->scratch, e->cap / 4, e->seg_len, e->seg_ff, e->chunk_tot, bsc);
                                 }
-                                hipLaunchKernelGGL(compact_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, (const uint8_t *) e->scratch, e->cap, e->seg_len, e->seg_ff,
-                                                   e->chunk_tot, e->n_seg, (uint8_t *) out_dev, pl.header, pl.header_len, out_capacity, pl.total, pl.base, bs);
+                                hipLaunchKernelGGL(compact_kernel, dim3((pl.n_seg + 3) / 4, frames), dim3(256), 0, st, (const uint8_t *) e->scratch, e->cap, e->seg_len, e->seg_ff,
+                                                   e->chunk_tot, pl.n_seg, (uint8_t *) out_dev, pl.header, pl.header_len, out_capacity, pl.total, pl.base, bsc);
                                 continue;
                         }
                         const int lrc = launch_coder(false, &pl);
@@ -2368,7 +2441,7 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                         if (frc != UG_HIP_SUCCESS) return frc;
                 } else {
                 hipLaunchKernelGGL(entropy_wave_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, e->cy, e->cb, e->cr, e->ca ? e->ca : e->cr, e->mcu_w, e->n_mcu,
-                                   e->hs, e->vs, e->ctab, e->nc, 0, e->ri, e->n_seg, e->scratch, e->cap / 4, e->seg_len, e->seg_ff, e->chunk_tot, bs);
+                                   e->hs, e->vs, e->hs * e->mcu_w, e->ctab, e->nc, 0, e->ri, e->n_seg, e->scratch, e->cap / 4, e->seg_len, e->seg_ff, e->chunk_tot, bs);
                 }
                 hipLaunchKernelGGL(compact_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, (const uint8_t *) e->scratch, e->cap, e->seg_len, e->seg_ff, e->chunk_tot,
                                    e->n_seg, (uint8_t *) out_dev, e->header_dev, (int) e->header.size(), out_capacity, e->total_host_dev, nullptr, bs);

@@ -484,6 +484,116 @@ __global__ __attribute__((amdgpu_waves_per_eu(3, 3))) __launch_bounds__(SUB == 4
         uyvy_jpeg_fast_body<SUB>(src, pitch, height, mcu_w, div, out_y, out_cb, out_cr, fs);
 }
 
+// Packed RGB (3 B/px) -> the R, G, B components of a 4:2:0 / 4:2:2 stream (UG_JPEG_INPUT_RGB) in one pass over the frame: R at full resolution over
+// its 2 mcu_w x vs mcu_h block grid, G and B box-averaged over 2x2 (4:2:0: (a + b + c + d + 2) >> 2) / 2x1 (4:2:2: (a + b + 1) >> 1) pixels -- a pair
+// that runs past the picture takes its last column / row again -- over mcu_w x mcu_h, all with the divisors `div`.  The blocks past a component
+// plane replicate that plane's own last sample (the clamp of fdct_quant_plane_kernel on the downsampled ceil(w / 2) x ceil(h / ry) plane), not
+// the pixels': each plane equals fdct_quant_plane_kernel's on the planes tests/jpeg_layout_bitstream.py downsample() makes.
+// The layout of uyvy_jpeg_fast_body: a workgroup = a strip of 32 MCUs; the R waves take one block row of the strip each (64 blocks, 24 B per
+// pixel row and lane, contiguous across the lanes), the last wave the 32 G blocks (lanes 0-31) and the 32 B blocks (lanes 32-63), re-reading
+// the strip's pixels (48 B per pixel row and lane) from L1 / L2, so HBM sees each byte once.  The two halves of that wave differ only in the
+// byte they take: v_alignbyte moves it to the positions 3p of the pixel row's words, so that both run the same instructions.  Any width,
+// height, pitch and alignment: a block that reaches past the picture, or rows that are not 4-byte aligned, load byte by byte with the clamps.
+// 3 B/px read, 3 B/px (4:2:0) / 4 B/px (4:2:2) written.
+template <int SUB>
+__global__ __launch_bounds__(SUB == 420 ? 192 : 128) void rgb_jpeg42x_kernel(const uint8_t *__restrict__ src, int pitch, int width, int height, int mcu_w,
+                                                                             const float *__restrict__ div, int16_t *__restrict__ out_r,
+                                                                             int16_t *__restrict__ out_g, int16_t *__restrict__ out_b, FrameStrides fs)
+{
+        fs.apply(blockIdx.z, src, out_r, out_g, out_b); // blockIdx.z = frame of the batch
+        constexpr int kRWaves = SUB == 420 ? 2 : 1, kRy = SUB == 420 ? 2 : 1; // R block rows per MCU; pixel rows per G / B sample
+        __shared__ __attribute__((aligned(16))) uint8_t lds_all[(kRWaves + 1) * kStoreRows * kLdsPitch];
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int mcu0 = blockIdx.x * 32, my = blockIdx.y;
+        const int mcus = min(32, mcu_w - mcu0); // MCUs of this strip that exist
+        uint8_t *lds = lds_all + wave * kStoreRows * kLdsPitch;
+        const bool words = !(pitch & 3) && !(3 & (uintptr_t) src); // every row starts 4-byte aligned
+        float b[64];
+        uint32_t w[32];
+        if (wave < kRWaves) {
+                const int bx = 2 * mcu0 + lane;   // R block column
+                const int brow = kRWaves * my + wave; // R block row
+                if (lane < 2 * mcus) {
+                        if (words && 8 * bx + 8 <= width && 8 * brow + 8 <= height) {
+#pragma unroll
+                                for (int r = 0; r < 8; r++) {
+                                        const uint32_t *p = (const uint32_t *) (src + (long) (8 * brow + r) * pitch + 24 * bx);
+                                        uint32_t q[6];
+#pragma unroll
+                                        for (int k = 0; k < 6; k++) q[k] = p[k];
+#pragma unroll
+                                        for (int c = 0; c < 8; c++) b[8 * r + c] = (float) ((q[(3 * c) >> 2] >> (8 * ((3 * c) & 3))) & 0xffu);
+                                }
+                        } else { // edge replication
+#pragma unroll
+                                for (int r = 0; r < 8; r++) {
+                                        const uint8_t *row = src + (long) min(8 * brow + r, height - 1) * pitch;
+#pragma unroll
+                                        for (int c = 0; c < 8; c++) b[8 * r + c] = (float) row[3L * min(8 * bx + c, width - 1)];
+                                }
+                        }
+                        fdct8x8(b);
+                        quant_pack(b, div, w);
+                }
+                const long first = (long) brow * (2 * mcu_w) + 2 * mcu0;
+                wave_store_blocks(w, lds, out_r + 64 * first, lane, 2 * mcus);
+        } else {
+                const int comp = lane >> 5, m = lane & 31; // 0 = G, 1 = B ; MCU within the strip
+                const uint32_t k = 1u + (uint32_t) comp;   // the component's byte in a pixel
+                if (m < mcus) {
+                        const int mx = mcu0 + m;
+                        if (words && 16 * mx + 16 <= width && 8 * kRy * (my + 1) <= height) {
+#pragma unroll
+                                for (int r = 0; r < 8; r++) {
+                                        uint32_t t[kRy][12]; // the pixel rows' 48 bytes, shifted by k bytes: the component of pixel p is byte 3p
+#pragma unroll
+                                        for (int v = 0; v < kRy; v++) {
+                                                const uint32_t *p = (const uint32_t *) (src + (long) (kRy * (8 * my + r) + v) * pitch + 48 * mx);
+                                                uint32_t q[12];
+#pragma unroll
+                                                for (int i = 0; i < 12; i++) q[i] = p[i];
+#pragma unroll
+                                                for (int i = 0; i < 12; i++) t[v][i] = __builtin_amdgcn_alignbyte(i < 11 ? q[i + 1] : 0u, q[i], k); // (byte 47 + k lies behind: not needed)
+                                        }
+#pragma unroll
+                                        for (int c = 0; c < 8; c++) {
+                                                uint32_t a = 0;
+#pragma unroll
+                                                for (int v = 0; v < kRy; v++) {
+#pragma unroll
+                                                        for (int dx = 0; dx < 2; dx++) {
+                                                                const int bi = 6 * c + 3 * dx;
+                                                                a += (t[v][bi >> 2] >> (8 * (bi & 3))) & 0xffu;
+                                                        }
+                                                }
+                                                b[8 * r + c] = (float) (SUB == 420 ? (a + 2u) >> 2 : (a + 1u) >> 1);
+                                        }
+                                }
+                        } else { // the plane's edge: clamp to the G / B plane, then each sample's pixels to the picture
+                                const int cw = (width + 1) / 2, ch = SUB == 420 ? (height + 1) / 2 : height;
+#pragma unroll
+                                for (int r = 0; r < 8; r++) {
+                                        const int gy = min(8 * my + r, ch - 1);
+                                        const uint8_t *r0 = src + (long) (kRy * gy) * pitch, *r1 = src + (long) min(kRy * gy + kRy - 1, height - 1) * pitch;
+#pragma unroll
+                                        for (int c = 0; c < 8; c++) {
+                                                const int gx = min(8 * mx + c, cw - 1);
+                                                const long x0 = 3L * (2 * gx) + k, x1 = 3L * min(2 * gx + 1, width - 1) + k;
+                                                uint32_t a = (uint32_t) r0[x0] + r0[x1];
+                                                if (SUB == 420) a += (uint32_t) r1[x0] + r1[x1];
+                                                b[8 * r + c] = (float) (SUB == 420 ? (a + 2u) >> 2 : (a + 1u) >> 1);
+                                        }
+                                }
+                        }
+                        fdct8x8(b);
+                        quant_pack(b, div, w);
+                }
+                // lanes 0-31 -> G blocks, lanes 32-63 -> B blocks of this strip: two contiguous 4 KiB stretches
+                const long first = (long) my * mcu_w + mcu0;
+                wave_store_blocks_two(w, lds, out_g + 64 * first, out_b + 64 * first, lane, mcus);
+        }
+}
+
 // T.81 Annex K tables (natural order) -- same data as oracle/jpeg_oracle.c by construction of the
 // standard; kept separately so the product never links the oracle.
 const uint8_t kLuma[64] = {
@@ -585,6 +695,36 @@ int ug::jpeg_fdct_quant_rgba4444(const void *src, int pitch, int width, int heig
         const long total = (long) blocks_w * blocks_h;
         hipLaunchKernelGGL(rgba_jpeg4444_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, (hipStream_t) stream,
                            (const uint8_t *) src, pitch, width, height, blocks_w, total, div, out_r, out_g, out_b, out_a);
+        UG_HIP_LAUNCH_CHECK();
+        return UG_HIP_SUCCESS;
+}
+
+// packed RGB (3 B/px) -> quantised blocks of a 4:2:0 / 4:2:2 R, G, B stream (rgb_jpeg42x_kernel), all with the divisors `div` (64 floats): R over
+// 2 mcu_w x vs mcu_h blocks, G and B over mcu_w x mcu_h; frame f of a batch reads src + f * src_stride and writes f * r_bytes / gb_bytes further on.
+// Declared in jpeg_entropy.hip
+namespace ug {
+int jpeg_fdct_quant_rgb42x(int sub, const void *src, int pitch, int width, int height, const float *div, int16_t *out_r, int16_t *out_g, int16_t *out_b,
+                           int frames, size_t src_stride, size_t r_bytes, size_t gb_bytes, ug_hip_stream_t stream);
+}
+int ug::jpeg_fdct_quant_rgb42x(int sub, const void *src, int pitch, int width, int height, const float *div, int16_t *out_r, int16_t *out_g, int16_t *out_b,
+                               int frames, size_t src_stride, size_t r_bytes, size_t gb_bytes, ug_hip_stream_t stream)
+{
+        if (!src || !div || !out_r || !out_g || !out_b || width <= 0 || height <= 0 || width > ug::kMaxDim || height > ug::kMaxDim || pitch < 3 * width ||
+            (sub != 420 && sub != 422) || frames < 1 || frames > 65535 || (15 & ((uintptr_t) out_r | (uintptr_t) out_g | (uintptr_t) out_b)) ||
+            (frames > 1 && ((r_bytes | gb_bytes) & 15))) {
+                ug::set_last_error_msg("jpeg_fdct_quant_rgb42x: bad arguments");
+                return UG_HIP_EINVAL;
+        }
+        const int mcu_w = (width + 15) / 16, mcu_h = sub == 420 ? (height + 15) / 16 : (height + 7) / 8;
+        const FrameStrides fs = { src_stride, r_bytes, gb_bytes };
+        const dim3 grid((unsigned) ((mcu_w + 31) / 32), (unsigned) mcu_h, (unsigned) frames);
+        if (sub == 420) {
+                hipLaunchKernelGGL((rgb_jpeg42x_kernel<420>), grid, dim3(192), 0, (hipStream_t) stream, (const uint8_t *) src, pitch, width, height, mcu_w, div,
+                                   out_r, out_g, out_b, fs);
+        } else {
+                hipLaunchKernelGGL((rgb_jpeg42x_kernel<422>), grid, dim3(128), 0, (hipStream_t) stream, (const uint8_t *) src, pitch, width, height, mcu_w, div,
+                                   out_r, out_g, out_b, fs);
+        }
         UG_HIP_LAUNCH_CHECK();
         return UG_HIP_SUCCESS;
 }

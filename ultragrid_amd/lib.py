@@ -27,6 +27,7 @@ TIES_EVEN, TIES_AWAY = 0, 1
 JPEG_CS_ASIS, JPEG_CS_RGB, JPEG_CS_YCBCR_BT601, JPEG_CS_YCBCR_BT601_256LVLS, JPEG_CS_YCBCR_BT709 = 0, 1, 2, 3, 4
 JPEG_NONINTERLEAVED = 1
 JPEG_INPUT_UYVY = 2
+JPEG_INPUT_RGB = 4  # a 4:2:0 / 4:2:2 encoder fed RGB, coding R, G, B components (UG_JPEG_INPUT_RGB)
 COPY_NO_WAIT, COPY_NO_JOIN = 1, 2
 ABI_VERSION = 5
 

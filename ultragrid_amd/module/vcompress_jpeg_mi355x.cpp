@@ -87,7 +87,9 @@ void usage()
                "\t\tsubsampling - JPEG subsampling; default = that of the codec the input is decoded to (get_best_decoder_from over\n"
                "\t\t              UYVY, RGB, RGBA): 422 for UYVY/YUYV/v210/Y216/DVS10, 444 (R,G,B components) for\n"
                "\t\t              RGB/RGBA/BGR/R10k/R12L/RG48/Y416/VUYA, 420 for I420; 420 from 4:2:2 input averages line pairs,\n"
-               "\t\t              444 from 4:2:2 input gives every pixel its pair's chroma (Y'CbCr, or R,G,B with :RGB)\n");
+               "\t\t              444 from 4:2:2 input gives every pixel its pair's chroma (Y'CbCr, or R,G,B with :RGB);\n"
+               "\t\t              422/420 from RGB-family input: Y'CbCr, or with :RGB R,G,B components (R 2x1 / 2x2, G and B\n"
+               "\t\t              box-averaged to 1x1; one scan per component unless :interleaved)\n");
 }
 
 /// the device-side decoder_t pass wire -> target; planar I420 (which has no decoder_t) with the reference's i420_8_to_uyvy shuffle
@@ -191,7 +193,8 @@ bool configure_with(state_video_compress_jpeg_mi355x *s, struct video_desc desc)
         // autoselect codes that codec's own subsampling: R,G,B 4:4:4 for an RGB-family target (R10k, R12L, RG48, but also Y416 and
         // VUYA: the ranking puts subsampling before colour space), 4:2:2 for UYVY (v210, Y216, YUYV, DVS10).  An RGBA target is fed as
         // RGB (the pad byte is ignored by GPUJPEG's 444_U8_P012Z too).  RGB-family targets with subsampling=422/420 go through
-        // the pixfmt_conv.c RGB->UYVY arithmetic.
+        // the pixfmt_conv.c RGB->UYVY arithmetic -- unless `:RGB` asks for R, G, B components: then the encoder is fed RGB and codes
+        // R at 2x2 / 2x1, G and B at 1x1 (UG_JPEG_INPUT_RGB).
         bool rgb_family = false;
         // Planar I420 goes to the encoder as it is (GPUJPEG_420_U8_P0P1P2, :335) -- unless an option asks for something a 4:2:0 planar picture is not
         // (another subsampling, BT.601, R,G,B): GPUJPEG resamples / converts such input in its preprocessor; here the picture is first brought to UYVY
@@ -218,22 +221,29 @@ bool configure_with(state_video_compress_jpeg_mi355x *s, struct video_desc desc)
         // color_space_internal (gpujpeg.cpp:303-305: the option, else RGB for RGB input and BT.709 for the rest).  4:4:4 from an RGB-family input: R, G, B
         // as they are, or converted to the Y'CbCr space asked for; 4:2:x (UYVY, or RGB-family input brought to UYVY with pixfmt_conv.c's BT.709
         // arithmetic): BT.709 limited range as the samples are, or converted to BT.601.  subsampling=444 on a 4:2:2 source: every pixel with its pair's
-        // chroma, coded as BT.709 / BT.601 Y'CbCr or as R, G, B.  Not done: R, G, B components subsampled (4:2:x + RGB); planar input converted.
+        // chroma, coded as BT.709 / BT.601 Y'CbCr or as R, G, B.  4:2:x with `:RGB` from an RGB-family input: R, G, B components, R at 2x2 / 2x1 and
+        // G, B box-averaged to 1x1 -- the layout the reference asks GPUJPEG for with subsampling=420/422 on RGB input (color_space_internal stays
+        // GPUJPEG_RGB, gpujpeg.cpp:295-305: same components, sampling factors and scans; the samples are unpinned towards libgpujpeg, whose
+        // preprocessor is not in the reference tree).  Not done: R, G, B components subsampled from a UYVY / I420 source; planar input converted.
         int enc_cs = UG_JPEG_CS_ASIS;
         const bool uyvy_as_444 = sub == 444 && !rgb_family;
+        const bool rgb_sub = sub != 444 && rgb_family && s->internal_cs == UG_JPEG_CS_RGB;
         if (uyvy_as_444) {
                 enc_cs = s->internal_cs;
         } else if (sub == 444) {
                 enc_cs = s->internal_cs == UG_JPEG_CS_RGB ? UG_JPEG_CS_ASIS : s->internal_cs;
+        } else if (rgb_sub) {
+                enc_cs = UG_JPEG_CS_RGB;
         } else if (s->internal_cs == UG_JPEG_CS_RGB) {
-                MSG(ERROR, "internal colour space RGB: R, G, B components are coded 4:4:4 only (add subsampling=444)\n");
+                MSG(ERROR, "internal colour space RGB: R, G, B components are subsampled from RGB-family input only (add subsampling=444)\n");
                 return false;
         } else if (s->internal_cs == UG_JPEG_CS_YCBCR_BT601 || s->internal_cs == UG_JPEG_CS_YCBCR_BT601_256LVLS) {
                 enc_cs = s->internal_cs;
         }
-        // one scan per component for RGB input unless `:interleaved` (gpujpeg.cpp:303) -- where the components are not subsampled (the reference
-        // writes subsampled RGB-input streams that way too; here those are 4:2:x Y'CbCr streams of one scan)
-        const int enc_flags = (rgb_family && sub == 444 && !s->force_interleaved ? UG_JPEG_NONINTERLEAVED : 0) | (uyvy_as_444 ? UG_JPEG_INPUT_UYVY : 0);
+        // one scan per component for RGB input unless `:interleaved` (gpujpeg.cpp:303) -- where the components stay R, G, B (4:4:4, or 4:2:x with `:RGB`);
+        // 4:2:x Y'CbCr streams from RGB-family input are one scan, as before
+        const int enc_flags = ((rgb_family && sub == 444) || rgb_sub ? (s->force_interleaved ? 0 : UG_JPEG_NONINTERLEAVED) : 0) |
+                              (uyvy_as_444 ? UG_JPEG_INPUT_UYVY : 0) | (rgb_sub ? UG_JPEG_INPUT_RGB : 0);
         if (s->alpha) { // gpujpeg.cpp:318-330
                 if (desc.color_spec == RGBA) {
                         MSG(ERROR, "alpha: a fourth component is not coded by this encoder (the reference needs GPUJPEG >= 0.20.2 for it, gpujpeg.cpp:410-413); "
@@ -244,7 +254,7 @@ bool configure_with(state_video_compress_jpeg_mi355x *s, struct video_desc desc)
         }
         if (planar_as_it_is) {
                 // (s->enc_in = I420, above)
-        } else if (sub == 444 && rgb_family) {
+        } else if ((sub == 444 && rgb_family) || rgb_sub) {
                 s->enc_in = UG_PF_RGB;
         } else {
                 s->enc_in = UG_PF_UYVY;
