@@ -326,6 +326,31 @@ int ug_hip_linesize(ug_pixfmt_t fmt, int width);
 int ug_hip_deinterlace_blend(void *frame_dev, size_t linesize, int lines, ug_hip_stream_t stream);
 int ug_hip_deinterlace_blend_batch(void *frame_dev, size_t linesize, int lines, int frames, size_t frame_stride, ug_hip_stream_t stream);
 
+/* The `scale` video postprocessor (src/vo_postprocess/scale.c, `-p scale:<w>:<h>`): bilinear resampling of UG_PF_RGBA or UG_PF_UYVY pictures,
+ * as the module's GL_LINEAR / GL_CLAMP_TO_EDGE texture draw computes it on Mesa llvmpipe (tests/golden/scale_gl_ref.npz) -- except next to position
+ * ties, where llvmpipe's fp32 texture coordinates and the exact positions below can differ by one step: at most 1 LSB per byte.  A picture is a texture
+ * of 4-byte texels -- one RGBA pixel, or one U Y0 V Y1 pair -- and with interlaced_merged two lines side by side form one texel row (twice as
+ * wide, half as high: the vertical filter stays in one field), in and out (scale.c:190-216).  Per axis, n_in -> n_out texels, output texel x:
+ *   p = round_half_up((2x + 1) * n_in * 128 / n_out) - 128;  i0 = p >> 8, i1 = i0 + 1 (both clamped to 0 .. n_in - 1);  w = p & 255
+ *   lerp(a, b, w) = (a * (256 - w) + b * w + 128) >> 8 per byte; rows after columns.  A downscale by more than 2 still reads 2 x 2 texels.
+ * Deviations from the reference's slips: a UYVY line is (width + 1) / 2 texels (vc_get_linesize), in and out (the reference's
+ * textures are width / 2 texels wide and its rows shear); interlaced_merged with an odd dst_height is refused (the reference leaves the last line
+ * unwritten); an odd src_height drops the last line, as there.
+ * Pitches 0 = vc_get_linesize; otherwise at least that and a multiple of 4; pointers 4-byte aligned; lines past the written line size keep their
+ * bytes.  Sizes 1..65536, at most INT_MAX bytes per frame, frames 1..65535 (grid.z), frame i at src + i * src_frame_stride -> dst + i *
+ * dst_frame_stride (strides multiples of 4 covering a frame).  Anything else: UG_HIP_EINVAL (format: UG_HIP_EUNSUPP) before any device call. */
+struct ug_scale_desc {
+        const void *src;            /* device */
+        void       *dst;            /* device */
+        ug_pixfmt_t format;         /* UG_PF_RGBA or UG_PF_UYVY */
+        int         interlaced_merged;
+        int         src_width, src_height, dst_width, dst_height; /* pixels */
+        size_t      src_pitch, dst_pitch;                         /* bytes per line */
+        int         frames;
+        size_t      src_frame_stride, dst_frame_stride;
+};
+int ug_hip_scale(const struct ug_scale_desc *d, ug_hip_stream_t stream);
+
 /* packed -> planar (to_planar.h:53-74) */
 int ug_hip_uyvy_to_i420(const void *src_dev, int src_pitch, void *y, int y_pitch, void *u, int u_pitch,
                         void *v, int v_pitch, int width, int height, ug_hip_stream_t stream); /* uyvy_to_i420, to_planar.c:343 */

@@ -2,13 +2,15 @@
 """Regenerates integration/ultragrid_mi355x.patch from the reference's configure.ac (default /root/reference).
 
 The patch is what a maintainer applies to an UltraGrid checkout (after integration/install.sh has copied the module sources in):
-four insertions into configure.ac, nothing removed --
+insertions into configure.ac, nothing removed --
   1. detection of libug_mi355x (--with-ug-mi355x=<prefix>) in front of the Libav section (that section needs the answer),
   2. the lavc conversion hook: HAVE_LAVC_CUDA_CONV with src/libavcodec/lavc_conv_mi355x.o in place of the two stubbed *_cuda.o objects
      (configure.ac:2056-2069 of the reference; the hook's declarations are the reference's own *_cuda.h headers),
   3. the six modules through the reference's add_module helper (configure.ac:243-259), behind the CUDA DXT section -- where rtdxt, uyvy
      and cuda_dxt are decided -- with MI355X_NO_UYVY_COMPRESS / MI355X_NO_RTDXT / MI355X_NO_CUDA_DXT defined for those configure left out,
   4. a line in the summary table,
+  6. the `scale` postprocessor stand-in (src/vo_postprocess/scale_mi355x.o) behind the Scale section, with MI355X_NO_SCALE_PP where
+     configure decided scale=no (the GL module is not built),
   5. the ldgm_gpu library (src/rtp/ldgm_gpu_mi355x.o) where LDGM is on and the CUDA ldgm_gpu is not built: in front of the LDGM GPU
      section's ENSURE_FEATURE_PRESENT, so that --enable-ldgm-gpu without CUDA succeeds when libug_mi355x is found (the detection of 1.
      runs earlier in configure.ac than the LDGM section).
@@ -92,6 +94,17 @@ fi
 
 '''
 
+SCALE = '''
+# -p scale without GL: the MI355X stand-in (scale_mi355x always; `scale` too where this configure run left the GL module out)
+if test "${found_ug_mi355x?}" = yes
+then
+        add_module vo_pp_scale_mi355x "src/vo_postprocess/scale_mi355x.o" "$UG_MI355X_LIB"
+        if test "${scale?}" != yes; then
+                AC_DEFINE([MI355X_NO_SCALE_PP], [1], [scale_mi355x also registers as -p scale])
+        fi
+fi
+'''
+
 SUMMARY = 'add_column "MI355X DXT/JPEG" "${ug_mi355x?}"\n'
 
 
@@ -124,6 +137,8 @@ def main():
     new = insert_before(new, "        AC_DEFINE([HAVE_LAVC], [1], [Build with LAVC support])", LAVC)
     # 3. behind the CUDA DXT section
     new = insert_after(new, "ENSURE_FEATURE_PRESENT([$cuda_dxt_req], [$cuda_dxt], [CUDA DXT not found])", MODULES)
+    # 6. the `scale` stand-in, behind the Scale section (where scale is decided)
+    new = insert_after(new, "ENSURE_FEATURE_PRESENT([$scale_req], [$scale], [Scale not found])", SCALE)
     # 5. the MI355X ldgm_gpu, in front of the LDGM GPU section's check
     new = insert_before(new, "ENSURE_FEATURE_PRESENT([$ldgm_gpu_req], [$ldgm_gpu], [LDGM accelerated GPU cannot be enabled (CUDA not found?)])", LDGM)
     # 4. summary table, behind "Lavc ..." keeps the list alphabetical enough: in front of OpenAPV

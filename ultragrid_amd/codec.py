@@ -108,6 +108,22 @@ def pixfmt_convert(in_fmt: int, out_fmt: int, src: torch.Tensor, w: int, h: int,
     return dst
 
 
+def scale(fmt: int, src: torch.Tensor, w: int, h: int, out_w: int, out_h: int, frames: int = 1, merged: bool = False,
+          src_pitch: int = 0, dst_pitch: int = 0, dst: torch.Tensor | None = None) -> torch.Tensor:
+    """`-p scale:<out_w>:<out_h>` (src/vo_postprocess/scale.c) on the device: `frames` pictures of h lines `src_pitch` bytes apart (0: packed),
+    back to back -> frames x out_h lines of `dst_pitch` (0: linesize(fmt, out_w)) bytes; fmt PF_RGBA or PF_UYVY."""
+    src = _u8(src)
+    sp, dp = src_pitch or linesize(fmt, w), dst_pitch or linesize(fmt, out_w)
+    if dst is None:
+        dst = torch.zeros(frames * dp * out_h, dtype=torch.uint8, device=src.device)
+    dst = _u8(dst)
+    if src.numel() < frames * sp * h or dst.numel() < frames * dp * out_h:
+        raise ValueError("tensor smaller than the frames it should hold")
+    d = L.ScaleDesc(src.data_ptr(), dst.data_ptr(), fmt, int(merged), w, h, out_w, out_h, sp, dp, frames, sp * h, dp * out_h)
+    L.check(L.load().ug_hip_scale(C.byref(d), _stream()), "ug_hip_scale")
+    return dst
+
+
 def uyvy_to_i420(src: torch.Tensor, w: int, h: int):
     src = _u8(src)
     cw, ch = (w + 1) // 2, (h + 1) // 2

@@ -136,7 +136,15 @@ SYMBOLS = {
     "ug_hip_jpeg_decoder_plane": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "ug_hip_jpeg_encoder_encode": (_i, [_vp, _i, _vp, _i, _vp, _sz, C.POINTER(_sz), _vp]),
     "ug_hip_jpeg_encoder_encode_batch": (_i, [_vp, _i, _i, _vp, _i, _sz, _vp, _sz, _sz, C.POINTER(_sz), _vp]),
+    "ug_hip_scale": (_i, [_vp, _vp]),
 }
+
+
+class ScaleDesc(C.Structure):
+    """struct ug_scale_desc (include/ug_mi355x.h): ug_hip_scale's geometry"""
+    _fields_ = [("src", _vp), ("dst", _vp), ("format", _i), ("interlaced_merged", _i), ("src_width", _i), ("src_height", _i),
+                ("dst_width", _i), ("dst_height", _i), ("src_pitch", _sz), ("dst_pitch", _sz), ("frames", _i),
+                ("src_frame_stride", _sz), ("dst_frame_stride", _sz)]
 
 
 class UgHipError(RuntimeError):
