@@ -351,6 +351,53 @@ struct ug_scale_desc {
 };
 int ug_hip_scale(const struct ug_scale_desc *d, ug_hip_stream_t stream);
 
+/* The de-interlacing postprocessors / capture filters (`-p deinterlace`, `deinterlace_blend`, `double_framerate[:d]`, `deinterlace_bob`,
+ * `deinterlace_linear`) on device frames of `lines` lines of `linesize` bytes, byte for byte what the reference's C computes:
+ *   UG_DEINT_BLEND   vc_deinterlace_ex (src/video_codec.c:722-854): dst[0] line y = (a + b + 1) >> 1 of src lines y and y + 1 per element, the last
+ *                    line = the destination's line above it; a single line is copied.  dst[0] may equal src (same pitch), as there.
+ *   UG_DEINT_WEAVE   perform_df (src/vo_postprocess/temporal-deint.c:240-277): dst[0] = even lines of src + odd lines of prev (the frame before),
+ *                    dst[1] = src; blend_after_weave (`:d`): vc_deinterlace_ex over each, in the same launch.
+ *   UG_DEINT_BOB     perform_bob (:279-300): dst[0] = every even line twice; dst[1] = line 1, then every odd line twice; where the height
+ *                    leaves a single last line it repeats the line above it.
+ *   UG_DEINT_LINEAR  perform_linear (:442-466): as BOB with the lines between two field lines interpolated by avg_lines (:307-440); the last
+ *                    one or two lines are copies of ONE source line, the first of them (the reference's source pointer stands still, :462-465).
+ * Elements: bytes (RGBA, UYVY, YUYV, RGB, BGR, VUYA), uint16_t (RG48, Y216, Y416), v210's three fields per word (10, 10 and -- as `v >> 20` --
+ * 12 bits), R10k's big-endian fields at bits 22 / 12 / 2 (the low two bits of every averaged word are zero, :797-803), R12L's stream of 12-bit
+ * samples (:807-846).  avg_lines of the 8- and 16-bit formats is NOT that average but (c1 >> 1) + (c2 >> 1) + (c1 & 1), c1 the upper line
+ * (temporal-deint.c:318-319,334-335), and its R10k words are read with ntohl but stored
+ * in host order (:388-393: the averaged lines of LINEAR come out byte-swapped): both reproduced.  Any other format: UG_HIP_EUNSUPP (the reference returns false; its modules copy / bob).
+ * An averaged line writes what the reference's loops reach and leaves the rest of the destination line as it was (WEAVE + blend: the woven bytes):
+ *   BLEND: v210 / R10k linesize / 16 * 16 bytes; 16-bit formats the same from 16 bytes on (the x86-64 build's tail loop, :759,769, compares a
+ *   byte offset with an element count and never runs behind its vector loop); R12L linesize / 36 groups of 8 words (a 36-byte group has 9: the last ninth of a line is
+ *   never written, :814-816), less the last word where it ends inside a sample.  LINEAR: v210 the same; R12L linesize / 16 groups of 4 words.
+ * Deviations, where the reference leaves its buffers: LINEAR R10k averages the one line (avg_lines walks four lines' worth,
+ * :385-387); 8- / 16-bit LINEAR writes linesize bytes (avg_lines_per_elem rounds up to 16, :314,330); WEAVE with an odd number of lines
+ * (:247-258) and BOB / LINEAR / WEAVE with one line are refused; lines == 0 (`lines - 1` underflows, :733) is refused; WEAVE + blend honours
+ * dst_pitch (the reference passes the line size as pitch, :270-273).
+ * Pitches 0 = linesize, otherwise at least that; linesize, pitches, strides and pointers multiples of the element size (1, 2, or 4 bytes for
+ * v210 / R10k / R12L); lines 1..65536, at most INT_MAX bytes per frame, frames 1..65535 (grid.z), frame i at src (prev) + i * src_frame_stride
+ * -> dst[k] + i * dst_frame_stride.  Sources and destinations must not overlap (but BLEND's dst[0] == src).  Anything else: UG_HIP_EINVAL
+ * before any device call.  16-byte aligned pointers, pitches and strides take the dwordx4 path. */
+#define UG_DEINT_BLEND  0
+#define UG_DEINT_WEAVE  1
+#define UG_DEINT_BOB    2
+#define UG_DEINT_LINEAR 3
+struct ug_deinterlace_desc {
+        const void *src;            /* device: the frame */
+        const void *prev;           /* device: the frame before it (WEAVE only; same pitch and stride as src) */
+        void       *dst[2];         /* device: the output of postprocess(in) and of postprocess(NULL); BLEND writes dst[0] only */
+        ug_pixfmt_t format;
+        int         mode;           /* UG_DEINT_* */
+        int         blend_after_weave;
+        int         lines;
+        size_t      linesize;       /* bytes */
+        size_t      src_pitch, dst_pitch;
+        int         frames;
+        size_t      src_frame_stride, dst_frame_stride;
+};
+int ug_hip_deinterlace(const struct ug_deinterlace_desc *d, ug_hip_stream_t stream);
+int ug_hip_deinterlace_supported(ug_pixfmt_t format, int mode); /* 1 / 0 */
+
 /* packed -> planar (to_planar.h:53-74) */
 int ug_hip_uyvy_to_i420(const void *src_dev, int src_pitch, void *y, int y_pitch, void *u, int u_pitch,
                         void *v, int v_pitch, int width, int height, ug_hip_stream_t stream); /* uyvy_to_i420, to_planar.c:343 */

@@ -124,6 +124,28 @@ def scale(fmt: int, src: torch.Tensor, w: int, h: int, out_w: int, out_h: int, f
     return dst
 
 
+def deinterlace(fmt: int, mode: int, src: torch.Tensor, linesize_bytes: int, lines: int, prev: torch.Tensor | None = None, frames: int = 1,
+                blend: bool = False, src_pitch: int = 0, dst_pitch: int = 0, dst: tuple | None = None, in_place: bool = False):
+    """The reference's de-interlacers on the device (ug_hip_deinterlace): mode L.DEINT_BLEND (vc_deinterlace_ex; returns one tensor; in_place:
+    over src itself), L.DEINT_WEAVE (double_framerate, `prev` = the frame before, blend = `:d`), L.DEINT_BOB, L.DEINT_LINEAR (these return the two
+    outputs).  `frames` pictures of `lines` lines `src_pitch` (0: linesize_bytes) apart, back to back, in and out."""
+    src = _u8(src)
+    sp, dp = src_pitch or linesize_bytes, dst_pitch or linesize_bytes
+    two = mode != L.DEINT_BLEND
+    if dst is None:
+        dst = (src if in_place else torch.zeros(frames * dp * lines, dtype=torch.uint8, device=src.device),
+               torch.zeros(frames * dp * lines, dtype=torch.uint8, device=src.device) if two else None)
+    if src.numel() < frames * sp * lines or any(t is not None and _u8(t).numel() < frames * dp * lines for t in dst):
+        raise ValueError("tensor smaller than the frames it should hold")
+    if mode == L.DEINT_WEAVE and (prev is None or _u8(prev).numel() < frames * sp * lines):
+        raise ValueError("WEAVE needs the previous frame(s)")
+    d = L.DeinterlaceDesc(src.data_ptr(), prev.data_ptr() if prev is not None else None,
+                          (L._vp * 2)(dst[0].data_ptr(), dst[1].data_ptr() if dst[1] is not None else None), fmt, mode, int(blend), lines,
+                          linesize_bytes, sp, dp, frames, sp * lines, dp * lines)
+    L.check(L.load().ug_hip_deinterlace(C.byref(d), _stream()), "ug_hip_deinterlace")
+    return (dst[0], dst[1]) if two else dst[0]
+
+
 def uyvy_to_i420(src: torch.Tensor, w: int, h: int):
     src = _u8(src)
     cw, ch = (w + 1) // 2, (h + 1) // 2

@@ -137,6 +137,8 @@ SYMBOLS = {
     "ug_hip_jpeg_encoder_encode": (_i, [_vp, _i, _vp, _i, _vp, _sz, C.POINTER(_sz), _vp]),
     "ug_hip_jpeg_encoder_encode_batch": (_i, [_vp, _i, _i, _vp, _i, _sz, _vp, _sz, _sz, C.POINTER(_sz), _vp]),
     "ug_hip_scale": (_i, [_vp, _vp]),
+    "ug_hip_deinterlace": (_i, [_vp, _vp]),
+    "ug_hip_deinterlace_supported": (_i, [_i, _i]),
 }
 
 
@@ -145,6 +147,15 @@ class ScaleDesc(C.Structure):
     _fields_ = [("src", _vp), ("dst", _vp), ("format", _i), ("interlaced_merged", _i), ("src_width", _i), ("src_height", _i),
                 ("dst_width", _i), ("dst_height", _i), ("src_pitch", _sz), ("dst_pitch", _sz), ("frames", _i),
                 ("src_frame_stride", _sz), ("dst_frame_stride", _sz)]
+
+
+DEINT_BLEND, DEINT_WEAVE, DEINT_BOB, DEINT_LINEAR = 0, 1, 2, 3
+
+
+class DeinterlaceDesc(C.Structure):
+    """struct ug_deinterlace_desc (include/ug_mi355x.h): ug_hip_deinterlace's frames and geometry"""
+    _fields_ = [("src", _vp), ("prev", _vp), ("dst", _vp * 2), ("format", _i), ("mode", _i), ("blend_after_weave", _i), ("lines", _i),
+                ("linesize", _sz), ("src_pitch", _sz), ("dst_pitch", _sz), ("frames", _i), ("src_frame_stride", _sz), ("dst_frame_stride", _sz)]
 
 
 class UgHipError(RuntimeError):
