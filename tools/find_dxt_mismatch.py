@@ -2,7 +2,8 @@
 """Random search for a DXT encode / decode call on which the GPU differs from the oracle: input formats x outputs, ANY width and height (round 6:
 half the draws are not multiples of 4 -- 4:2:2 formats keep an even width; v210 widths that are not a multiple of 12 included), padded pitches, bottom-up sources, both tie rules, content from
 flat over gradients to noise and extreme values; every encoded frame is also decoded on both sides.  GPU box.
-usage: python tools/find_dxt_mismatch.py [n]"""
+usage: python tools/find_dxt_mismatch.py [n] [inputs] [encode]
+  inputs: comma-separated subset of RGB,RGBA,UYVY,v210 to draw from (default: all four); "encode": skip the decode legs"""
 import os
 import sys
 
@@ -20,10 +21,14 @@ OUTS = [(po.OUT_DXT1, L.DXT1), (po.OUT_DXT5YCOCG, L.DXT5_YCOCG)]
 
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
+    combos = [c for c in COMBOS if len(sys.argv) < 3 or c[0] in sys.argv[2].split(",")]
+    if not combos:
+        sys.exit(f"find_dxt_mismatch: no input format in {sys.argv[2]!r}; choose from {','.join(c[0] for c in COMBOS)}")
+    decode = "encode" not in sys.argv[3:]
     bad = 0
     for seed in range(n):
         rng = np.random.default_rng(seed)
-        name, pin, pf, bpp = COMBOS[int(rng.integers(len(COMBOS)))]
+        name, pin, pf, bpp = combos[int(rng.integers(len(combos)))]
         pout, oid = OUTS[int(rng.integers(2))]
         w, h = 4 * int(rng.integers(1, 90)), 4 * int(rng.integers(1, 12))
         if rng.random() < 0.5:                                                # any size (dxt_util.h:59-67): the EDGE instantiations
@@ -71,7 +76,7 @@ def main():
             if not np.array_equal(gb, np.concatenate(singles)):
                 print("BATCH MISMATCH", seed, name, w, hh, pitch, frames, stride, flush=True)
                 bad += 1
-        for out in ("RGBA", "RGB", "UYVY"):
+        for out in ("RGBA", "RGB", "UYVY") if decode else ():
             if out == "UYVY" and w % 2:
                 continue
             dw = po.dxt_decode(pout, out, want, w, h, ties=ties)

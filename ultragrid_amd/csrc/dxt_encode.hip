@@ -150,6 +150,25 @@ __device__ __forceinline__ uint32_t spread16(uint32_t x)
 #ifndef UG_DXT5_ALPHA_GROUP
 #define UG_DXT5_ALPHA_GROUP 8
 #endif
+// DXT5-YCoCg colour stage: 4:2:2 sources hold ONE chroma sample per horizontal pixel pair, so the pair is located on the palette
+// segment once, from its even pixel (1 = on; 0 = every pixel located on its own; A/B switch).  Only loaders with kChromaPairs take it.
+#ifndef UG_DXT_PAIR_ZONE
+#define UG_DXT_PAIR_ZONE 1
+#endif
+// DXT5-YCoCg fast stages: the row of the lookup table is read from the mantissa of fma(u, rows - 1, 2^23) instead of
+// v_cvt_u32_f32(u * rows) (1 = on; A/B switch).  kIndexBias + n, n = 0 .. 7, is the integer 2^23 + n: one ulp = 1 in that binade.
+#ifndef UG_DXT_BITS_INDEX
+#define UG_DXT_BITS_INDEX 1
+#endif
+[[maybe_unused]] constexpr float kIndexBias = 8388608.0f;      // 2^23
+[[maybe_unused]] constexpr uint32_t kIndexBits = 0x4b000000u;  // its bits: lowest set bit 24, so kIndexBits << 8 == 0 (mod 2^32) -- a row offset needs no correction
+// what `fields` accumulations acc = (acc << shift) + (kIndexBits + n) leave in a 32-bit word besides the n (wrap-around arithmetic)
+constexpr uint32_t index_bias_sum(int fields, int shift)
+{
+        uint32_t s = 0;
+        for (int n = 0; n < fields && n * shift < 32; n++) s += kIndexBits << (n * shift);
+        return s;
+}
 // Diagnostics (ug_hip_dxt_encode_stats): waves that left a fast index stage for the reference's full form, counted in those (cold) paths only
 __device__ unsigned long long g_full_form_waves[2]; // [0] colour indices, [1] alpha indices
 __device__ __forceinline__ void count_full_form(int which)
@@ -202,6 +221,7 @@ struct Loader;
 template <bool YUV>
 struct Loader3 {
         static constexpr int kBlocks = 1;
+        static constexpr bool kChromaPairs = false; // every pixel has its own chroma
         uint32_t w[4][3];
         template <bool EDGE = false>
         __device__ __forceinline__ void load(const uint8_t *src, uint32_t pitch, uint32_t unit_x, const int (&rows)[4])
@@ -256,6 +276,7 @@ struct Loader3 {
 // ---- RGBA: 16 B per block row, alpha ignored (compress_dxt1_fp.glsl:41 reads .rgb) ----
 struct LoaderRGBAWords {
         static constexpr int kBlocks = 1;
+        static constexpr bool kChromaPairs = false; // every pixel has its own chroma
         uint4 w[4];
         template <bool EDGE = false>
         __device__ __forceinline__ void load(const uint8_t *src, uint32_t pitch, uint32_t unit_x, const int (&rows)[4])
@@ -297,6 +318,7 @@ struct LoaderRGBAWords {
 template <bool CONVERT>
 struct LoaderUYVY {
         static constexpr int kBlocks = 1;
+        static constexpr bool kChromaPairs = CONVERT; // pixels 2j, 2j + 1 of a row come out of one yuv_pair_to_rgb call (raw Y,Cb,Cr in the RGB channels: the pair shares g and b only, not Co / Cg)
         uint2 w[4];
         template <bool EDGE = false>
         __device__ __forceinline__ void load(const uint8_t *src, uint32_t pitch, uint32_t unit_x, const int (&rows)[4])
@@ -356,6 +378,7 @@ struct ConvTables {
 template <bool CONVERT>
 struct LoaderUYVYLds {
         static constexpr int kBlocks = 1;
+        static constexpr bool kChromaPairs = CONVERT; // pixels 2j, 2j + 1 of a row come out of one yuv_pair_to_rgb call (raw Y,Cb,Cr in the RGB channels: the pair shares g and b only, not Co / Cg)
         static constexpr bool kLdsConv = CONVERT;
         uint2 w[4];
         const ConvTables *lut;
@@ -421,6 +444,7 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 template <bool CONVERT>
 struct LoaderUYVYTyped {
         static constexpr int kBlocks = 1;
+        static constexpr bool kChromaPairs = CONVERT; // pixels 2j, 2j + 1 of a row come out of one yuv_pair_to_rgb call (raw Y,Cb,Cr in the RGB channels: the pair shares g and b only, not Co / Cg)
         f32x4 f[4][2];
         // width = 2 (mod 4): one U Y0 V Y1 group exists; the second one repeats its last pixel: U Y1 V Y1.  (float) byte is what the
         // USCALED typed load returns.
@@ -494,6 +518,7 @@ template <> struct Loader<UG_PF_RGBA> : LoaderRGBAWords {};
 template <>
 struct Loader<UG_PF_V210> {
         static constexpr int kBlocks = 3;
+        static constexpr bool kChromaPairs = true; // pixels 2j, 2j + 1 of a row come out of one yuv_pair_to_rgb call
         uint32_t w[4][8];
         template <bool EDGE = false> // (a v210 line is padded to 128 bytes whatever the width, video_codec.c:507-521: whole units are always there)
         __device__ __forceinline__ void load(const uint8_t *src, uint32_t pitch, uint32_t unit_x, const int (&rows)[4])
@@ -540,7 +565,8 @@ struct Loader<UG_PF_V210> {
 // ---------------------------------------------------------------------------------------
 // DXT5-YCoCg block encode (compress_dxt5ycocg_fp.glsl:326-377 / cuda_dxt.cu:471-509)
 // ---------------------------------------------------------------------------------------
-template <bool AWAY>
+// PAIRS: pixels 2j, 2j + 1 of a row share their chroma sample (Loader::kChromaPairs)
+template <bool AWAY, bool PAIRS>
 __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &tab)
 {
         // ConvertRGBToYCoCg (glsl:27-34).  2.0*x and *0.25 are exact (powers of two), so
@@ -691,9 +717,24 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         float *const ta = tab.alpha;
                         ta[0 * 64] = T7; ta[1 * 64] = T6; ta[2 * 64] = T5; ta[3 * 64] = T4;
                         ta[4 * 64] = T3; ta[5 * 64] = T2; ta[6 * 64] = T1; ta[7 * 64] = -__builtin_inff();
+#if UG_DXT_BITS_INDEX
+                        // The same g without the conversion: u = (t - 1/2) / 7 = 6.5/7 - (a - mnY) / range with the clamp modifier (luma of
+                        // YUV sources can lie far outside [mnY, mxY]), then r = fma(u, 7, 2^23): r is the integer 2^23 + RN(7 u), so the low
+                        // bits of its pattern are g' = RN(clamp(t - 1/2, 0, 7)) = 0 .. 7.  g' = trunc(t) except where t is within its error
+                        // (< 6e-4 steps as above: rcp 1 ulp, mnY * inv rounded at magnitude <= 1024, two fma roundings) of an integer, or
+                        // exactly on it, where g' may be the neighbour of trunc(t).  There a lies 1/2 step from both nearest thresholds and
+                        // both rows give the same count: row g: g + (a <= D_(g+1)) = g + 1 (D_(g+1) is 1/2 step ABOVE a), row g + 1:
+                        // g + 1 + (a <= D_(g+2)) = g + 1 (D_(g+2) is 1/2 step BELOW a) -- the 0.49-step argument above covers either.
+                        // These fma are locating arithmetic only: no result of theirs is an operation of the reference.
+                        // The pattern kIndexBits + g' is used as it is: << 8 (the row offset) drops kIndexBits altogether, and the
+                        // index words collect it as a known sum that is subtracted once per word (the true words are 30 and 18 bits).
+                        const float inv = __builtin_amdgcn_rcpf(range);
+                        const float t0 = __builtin_fmaf(mnY, inv, (float) (6.5 / 7.0)), ninv = -inv;
+#else
                         // t / 8 with the clamp modifier (luma of YUV sources can lie far outside [mnY, mxY]: g must stay in 0..7), then * (8 - ulp)
                         const float inv = 0.875f * __builtin_amdgcn_rcpf(range);
                         const float t0 = __builtin_fmaf(mnY, inv, 0.875f), ninv = -inv;
+#endif
                         constexpr int kA = UG_DXT5_ALPHA_GROUP;
 #pragma unroll
                         for (int h = 16 / kA - 1; h >= 0; h--) { // groups of kA pixels: kA table reads in flight, bounded register use
@@ -701,8 +742,13 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                 uint32_t g[kA];
 #pragma unroll
                                 for (int j = kA - 1; j >= 0; j--) {
+#if UG_DXT_BITS_INDEX
+                                        g[j] = __float_as_uint(__builtin_fmaf(clamp01(__builtin_fmaf(Y[kA * h + j], ninv, t0)), 7.0f, kIndexBias));
+                                        D[j] = *(const float *) ((const char *) ta + (uint32_t) (g[j] << 8)); // rows of 64 floats
+#else
                                         g[j] = cvt_u32_sat(clamp01(__builtin_fmaf(Y[kA * h + j], ninv, t0)) * 7.9999995f);
                                         D[j] = ta[g[j] * 64];
+#endif
                                 }
                                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -713,6 +759,10 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                 }
                                 __builtin_amdgcn_sched_barrier(0);
                         }
+#if UG_DXT_BITS_INDEX
+                        lo -= index_bias_sum(10, 3);
+                        hi -= index_bias_sum(6, 3);
+#endif
                 } else
 #endif
 #ifdef UG_FORCE_ALPHA_LINEAR // test build: always take the reference-form path (tests/test_gpu_dxt.py)
@@ -795,6 +845,27 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 //   places by < 2e-7 absolute = < 6e-5 of a segment with vv >= 1e-5 (a non-zero segment of 8-bit-expanded end points
                 //   has vv >= 1.5e-5), and s itself is estimated to < 3e-4 (reciprocal + 5 roundings at magnitudes <= 650).
                 // A wave that holds a block outside that precondition (coincident end points over non-flat chroma) runs the full form below for all lanes.
+                //
+                // One location per chroma pair (PAIRS, UG_DXT_PAIR_ZONE).  The two pixels of a 4:2:2 pair come out of one yuv_pair_to_rgb
+                // call: U, V and the products rv, gu, gv, bu are shared, only the luma term differs, and it cancels in Co = (r - b) / 2 + off
+                // and Cg = (2 g - r - b) / 4 + off.  What is left is rounding: r, g, b, 2 g - r and (2 g - r) - b are rounded at magnitudes
+                // < 4 (<= 2^-23 each), r - b and the final sums at magnitudes < 2 (<= 2^-24), which adds up to
+                //   |dCo| <= 3.5 * 2^-23,  |dCg| <= 4 * 2^-23 < 5e-7
+                // between the pixels of a pair (tests/test_dxt_pair_chroma_bound.py evaluates the statements in strict fp32 over every
+                // (U, V) and finds 2.4e-7 for both).  The projection moves by |dCo ka + dCg kb| <= 5e-7 * sqrt(2) / sqrt(vv) < 2.3e-4 of the
+                // segment with vv >= 1e-5.  So the zone found for the even pixel locates the odd one to < 3e-4 + 2.3e-4, and with the
+                // rounded row (UG_DXT_BITS_INDEX, below) to < 7e-4: m >= 1/12 - 7e-4 still leaves > 200 x the rounding error.
+                // A pair that straddles 1/3 or 2/3 needs no care: there either zone's formula gives the same index (at 1/3: 2 b2 = 2 =
+                // 2 + b4, both 1/6 from their bisectors; at 2/3: 2 + b4 = 3 = 1 + 2 b3) -- the argument that lets a single pixel be
+                // placed in either zone.  Each pixel of the pair then evaluates ITS OWN open comparison against that palette pair,
+                // operands and order as in the reference.  The precondition below is the one of the per-pixel form: which waves take
+                // which form stays a property of the content.
+                //
+                // Row from float bits (UG_DXT_BITS_INDEX): u = (3 s - 1/2) / 2 with the clamp modifier, r = fma(u, 2, 2^23) is the integer
+                // 2^23 + RN(clamp(3 s - 1/2, 0, 2)): zone 0 for 3 s < 1, 1 up to 2, 2 above -- trunc(3 s) except within the error of s
+                // around the borders (and RN's tie on them), which is the case of the paragraph above.  3/2 and -1/4 fold into ka, kb, kc.
+                // These fma only locate; no result of theirs is an operation of the reference.  kIndexBits << 10 (rows of 64 float4)
+                // is 0 mod 2^32, and the zone word collects kIndexBits as a known sum, subtracted once.
                 const float vx = cx[1] - cx[0], vy = cy[1] - cy[0];
                 const float vv = vx * vx + vy * vy;
                 const float e0 = fmaxf(fmaxf(mxCo, cx[0]), cx[1]) - fminf(fminf(mnCo, cx[0]), cx[1]);
@@ -808,21 +879,34 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         tc[0 * 64] = make_float4(cx[0], cy[0], cx[2], cy[2]); // zone 0: d0 > d2
                         tc[1 * 64] = make_float4(cx[2], cy[2], cx[3], cy[3]); // zone 1: d2 > d3
                         tc[2 * 64] = make_float4(cx[1], cy[1], cx[3], cy[3]); // zone 2: d1 > d3
+#if UG_DXT_BITS_INDEX
+                        const float inv = 1.5f * __builtin_amdgcn_rcpf(vv);
+                        const float ka = vx * inv, kb = vy * inv;
+                        const float kc = -(cx[0] * ka + cy[0] * kb) - 0.25f;
+#else
                         const float inv = __builtin_amdgcn_rcpf(vv);
                         const float ka = vx * inv, kb = vy * inv;
                         const float kc = -(cx[0] * ka + cy[0] * kb);
+#endif
                         uint32_t zones = 0, open = 0; // 2-bit zone per pixel; the open comparison's result, one bit per pixel
                         // groups of kC pixels, the table reads of the next group issued before the distances of this one
                         constexpr int kC = UG_DXT5_FAST_GROUP, kGroups = 16 / kC;
-                        float4 e[2][kC];
-                        uint32_t kk[2][kC];
+                        constexpr int kP = PAIRS && UG_DXT_PAIR_ZONE ? 2 : 1; // pixels per location
+                        static_assert(kC % kP == 0, "a group holds whole pairs");
+                        float4 e[2][kC / kP];
+                        uint32_t kk[2][kC / kP];
                         auto fetch = [&](int grp, int slot) {
 #pragma unroll
-                                for (int j = kC - 1; j >= 0; j--) {
+                                for (int j = kC - kP; j >= 0; j -= kP) {
                                         const int i = kC * grp + j;
                                         const float s = clamp01(__builtin_fmaf(Co[i], ka, __builtin_fmaf(Cg[i], kb, kc)));
-                                        kk[slot][j] = cvt_u32_sat(s * 2.9999998f); // 0, 1, 2
-                                        e[slot][j] = tc[kk[slot][j] * 64];
+#if UG_DXT_BITS_INDEX
+                                        kk[slot][j / kP] = __float_as_uint(__builtin_fmaf(s, 2.0f, kIndexBias)); // kIndexBits + 0, 1, 2
+                                        e[slot][j / kP] = *(const float4 *) ((const char *) tc + (uint32_t) (kk[slot][j / kP] << 10));
+#else
+                                        kk[slot][j / kP] = cvt_u32_sat(s * 2.9999998f); // 0, 1, 2
+                                        e[slot][j / kP] = tc[kk[slot][j / kP] * 64];
+#endif
                                 }
                         };
                         fetch(kGroups - 1, (kGroups - 1) & 1);
@@ -836,13 +920,21 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
 #pragma unroll
                                 for (int j = kC - 1; j >= 0; j--) {
                                         const int i = kC * grp + j;
-                                        const float4 q = e[slot][j];
+                                        const float4 q = e[slot][j / kP];
                                         const float ax = Co[i] - q.x, ay = Cg[i] - q.y, bx = Co[i] - q.z, by = Cg[i] - q.w;
                                         const float da = ax * ax + ay * ay, db = bx * bx + by * by; // glsl:231-235, same operation order
-                                        zones = (zones << 2) + kk[slot][j];
+                                        if (j % kP == 0) { // one field of 2 * kP bits per location
+                                                zones = (zones << (2 * kP)) + kk[slot][j / kP];
+                                        }
                                         open = shift_in(open, LANEMASK(da > db));
                                 }
                                 __builtin_amdgcn_sched_barrier(0);
+                        }
+#if UG_DXT_BITS_INDEX
+                        zones -= index_bias_sum(16 / kP, 2 * kP);
+#endif
+                        if (kP == 2) { // pair j's zone sits in bits 4j, 4j + 1 = the field of pixel 2j: copy it to pixel 2j + 1's
+                                zones |= zones << 2;
                         }
                         const uint32_t c = spread16(open), k0 = zones & 0x55555555u, k1 = (zones >> 1) & 0x55555555u;
                         w_cidx = ((k0 & c) | k1) | ((k0 | c) << 1);
@@ -1189,7 +1281,7 @@ __global__ __launch_bounds__(256, (Loader<IN>::kBlocks > 1 ? 1 : UG_DXT_MIN_WAVE
                                 cur.block(k, p);
                         }
                         if (OUT == UG_DXT5_YCOCG) {
-                                res[k] = encode_dxt5ycocg<AWAY>(p, tab);
+                                res[k] = encode_dxt5ycocg<AWAY, L::kChromaPairs>(p, tab);
                         } else {
                                 const uint2 e = encode_dxt1<AWAY>(p, tab);
                                 res[k] = make_uint4(e.x, e.y, 0, 0);
