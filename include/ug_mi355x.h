@@ -223,7 +223,12 @@ int ug_hip_yuv422_to_yuv444(const void *src, void *out, int pix_count, ug_hip_st
 /* `in` in {UG_DXT1, UG_DXT5_YCOCG}; `out` in {UG_PF_RGB, UG_PF_BGR, UG_PF_RGBA, UG_PF_UYVY}.  RGBA output honours
  * rshift/gshift/bshift exactly like the decompress modules' reconfigure() arguments (video_decompress.h:85-100);
  * UYVY follows dxt_compress/rgba_to_yuv422.glsl.  dst_pitch 0 = packed.  Any width, height >= 1 (UYVY: even width): the stream
- * holds (width+3)/4 x (height+3)/4 blocks, width x height pixels are written (dxt_compress/dxt_decoder.c:146-149,368-389). */
+ * holds (width+3)/4 x (height+3)/4 blocks, width x height pixels are written (dxt_compress/dxt_decoder.c:146-149,368-389).
+ * Pitch and alignment: dst_dev is 16-byte aligned, src_dev 16-byte (DXT5) or 8-byte (DXT1, DXT1_YUV) aligned.  dst_pitch is at least the
+ * line (4, 3, 3, 2 bytes per pixel) and, with width and height both multiples of 4, a multiple of 16 (RGBA), 8 (UYVY) or 4 (RGB, BGR) --
+ * a row of a block leaves as one 128-, 64- or 32-bit store; with any other size a multiple of 4 (RGBA, UYVY) or any value (RGB, BGR).
+ * Only the width x height pixels are written: line padding and whatever follows the last line stay as they were.  Anything else is
+ * UG_HIP_EINVAL, and nothing is written. */
 int ug_hip_dxt_decode(ug_dxt_t in, ug_pixfmt_t out, const void *src_dev, void *dst_dev, int width, int height,
                       int dst_pitch, int rshift, int gshift, int bshift, ug_hip_stream_t stream);
 /* Same with the tie rule given explicitly (UG_DXT_TIES_*): it decides the float -> unorm8 writes of the UYVY output pass and of the
@@ -299,7 +304,16 @@ int ug_hip_pixfmt_best(ug_pixfmt_t in, const ug_pixfmt_t *candidates, ug_pixfmt_
  * 0/8/16, pixfmt_conv.h:62-65).  Pitches 0 = vc_get_linesize().
  * out = UG_PF_UYVY_GL (in = UG_PF_RGB or UG_PF_RGBA; any other input, or UG_PF_UYVY_GL as input: UG_HIP_EUNSUPP): output pixel pair i of
  * a line = rgba_to_yuv422.glsl's fp32 arithmetic on pixels 2i and 2i + 1 (for odd widths the last pair repeats the last pixel, GL's
- * CLAMP_TO_EDGE), float -> unorm8 with ties to even, alpha ignored, lines read at the given pitch (packed: 3 / 4 bytes per pixel). */
+ * CLAMP_TO_EDGE), float -> unorm8 with ties to even, alpha ignored, lines read at the given pitch (packed: 3 / 4 bytes per pixel).
+ * Pitch and alignment: a pitch is at least vc_get_size(width, format); bytes [0, vc_get_size(width, out)) of a destination line are the
+ * converter's, the rest of the pitch and everything around the picture is never written.  Alignment decides the speed, not the result:
+ *   - the pairs among v210, UYVY, YUYV, RGB, BGR, RGBA and RG48 -> UYVY (and in == out) take any base address and any pitch;
+ *   - in the other pairs of decoders[] the formats addressed as 16- or 32-bit words need base AND pitch aligned to them (as the reference
+ *     asserts): 4 bytes for a v210 / DVS10 source and for an RGBA, UYVY, VUYA, v210 or R10k destination (R10k from R12L / Y416: bytes),
+ *     2 bytes for RG48, Y216, Y416 on either side; RGB, R12L, and RGBA / UYVY / YUYV / VUYA / R10k / R12L sources are bytes.
+ *     A call below that is refused with UG_HIP_EINVAL and writes nothing;
+ *   - the 128-bit kernels run when both bases and both pitches are 16-byte aligned (a ragged end of the line, or the whole line
+ *     otherwise, takes the byte- and word-wise kernels: same bytes). */
 int ug_hip_pixfmt_convert(ug_pixfmt_t in, ug_pixfmt_t out, const void *src_dev, void *dst_dev,
                           int width, int height, int src_pitch, int dst_pitch,
                           int rshift, int gshift, int bshift, ug_hip_stream_t stream);

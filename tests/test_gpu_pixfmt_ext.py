@@ -141,6 +141,19 @@ def test_exported_line_functions(hip, po, func, bpp_in, bpp_out):
         assert rc == 0
         torch.cuda.synchronize()
         assert np.array_equal(ddst.cpu().numpy(), want), (func, w, h)
+        # dst_len is the caller's, not the width's: lines cut short by 1 and 5 bytes, one pixel, one byte -- the whole buffer, 0xA5 in the
+        # pitch's 8 spare bytes and behind the picture included (what the reference writes past such a dst_len, if anything, is expected too)
+        for dst_len in (w * bpp_out - 1, w * bpp_out - 5, bpp_out, 1):
+            want = aligned(dp * h + 64)
+            want[:] = 0xA5
+            for y in range(h):
+                fn(want.ctypes.data + y * dp, src.ctypes.data + y * sp, dst_len, 16, 0, 8)
+            ddst = torch.full((dp * h + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+            rc = hip.L.load().ug_hip_pixfmt_line_func(func.encode(), dsrc.data_ptr(), ddst.data_ptr(), w, h, sp, dp, dst_len, 16, 0, 8, None)
+            assert rc == 0, (func, w, h, dst_len)
+            torch.cuda.synchronize()
+            got = ddst.cpu().numpy()
+            assert np.array_equal(got, want), (func, w, h, dst_len, np.flatnonzero(got != want)[:16].tolist())
 
 
 def test_best_decoder_choice_equals_the_reference(po):

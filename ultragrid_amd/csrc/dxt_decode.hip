@@ -587,6 +587,11 @@ extern "C" int ug_hip_dxt_decode_ex(ug_dxt_t in, ug_pixfmt_t out, const void *sr
                 dst_pitch = ug::linesize(out, width);
         }
         if (dst_pitch < 0 || !ug::span_ok(dst_pitch, height)) return ug::refuse_size("ug_hip_dxt_decode");
+        // a pitch below the line would lay the lines over each other (an unknown output format is answered below)
+        if ((out == UG_PF_RGBA || out == UG_PF_RGB || out == UG_PF_BGR || out == UG_PF_UYVY) && dst_pitch < ug::linesize(out, width)) {
+                ug::set_last_error_msg("ug_hip_dxt_decode: dst_pitch is smaller than a line of the output format");
+                return UG_HIP_EINVAL;
+        }
         OutArgs o = { (uint8_t *) dst_dev, dst_pitch, rshift, gshift, bshift };
         hipStream_t st = (hipStream_t) stream;
         switch (out) {
