@@ -14,7 +14,7 @@ cp "$ROOT/include/ug_mi355x.h"               "$UG/include/ug_mi355x.h"
 cp "$M/vcompress_dxt_mi355x.cpp"             "$UG/src/video_compress/dxt_mi355x.cpp"
 cp "$M/vcompress_jpeg_mi355x.cpp"            "$UG/src/video_compress/jpeg_mi355x.cpp"
 cp "$M/vcompress_uyvy_mi355x.cpp"            "$UG/src/video_compress/uyvy_mi355x.cpp"
-cp "$M/ug_codec_map.h" "$M/mi355x_frame_sharder.h" "$UG/src/video_compress/"
+cp "$M/ug_codec_map.h" "$M/mi355x_frame_sharder.h" "$M/mi355x_tile_encoder.h" "$M/mi355x_hip_device.h" "$UG/src/video_compress/"
 cp "$M/vdecompress_dxt_mi355x.c"             "$UG/src/video_decompress/dxt_mi355x.c"
 cp "$M/vdecompress_jpeg_mi355x.c"            "$UG/src/video_decompress/jpeg_mi355x.c"
 cp "$M/vdecompress_jpeg_to_dxt_mi355x.c"     "$UG/src/video_decompress/jpeg_to_dxt_mi355x.c"

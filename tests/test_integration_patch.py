@@ -46,7 +46,8 @@ def test_install_places_the_sources_and_patches_configure(tmp_path):
     assert after.index("found_ug_mi355x=no") < after.index("# Libav") < after.index('test "$found_ug_mi355x" = yes')
     assert after.index("add_module() {") < after.index("add_module vcompress_dxt ")
     for f in ("include/ug_mi355x.h", "src/video_compress/dxt_mi355x.cpp", "src/video_compress/jpeg_mi355x.cpp", "src/video_compress/ug_codec_map.h",
-              "src/video_compress/mi355x_frame_sharder.h", "src/video_decompress/dxt_mi355x.c", "src/video_decompress/jpeg_mi355x.c",
+              "src/video_compress/mi355x_frame_sharder.h", "src/video_compress/mi355x_tile_encoder.h", "src/video_compress/mi355x_hip_device.h",
+              "src/video_compress/uyvy_mi355x.cpp", "src/video_decompress/dxt_mi355x.c", "src/video_decompress/jpeg_mi355x.c",
               "src/video_decompress/jpeg_to_dxt_mi355x.c", "src/video_decompress/mi355x_receiver.h", "src/libavcodec/lavc_conv_mi355x.cpp"):
         assert (ug / f).is_file(), f
     # a second run leaves the tree as it is
@@ -56,6 +57,7 @@ def test_install_places_the_sources_and_patches_configure(tmp_path):
 
 
 @pytest.mark.parametrize("src,std", [("src/video_compress/dxt_mi355x.cpp", "gnu++20"), ("src/video_compress/jpeg_mi355x.cpp", "gnu++20"),
+                                     ("src/video_compress/uyvy_mi355x.cpp", "gnu++20"),
                                      ("src/video_decompress/dxt_mi355x.c", "gnu2x"), ("src/video_decompress/jpeg_mi355x.c", "gnu2x"),
                                      ("src/video_decompress/jpeg_to_dxt_mi355x.c", "gnu2x")])
 def test_installed_sources_compile_where_they_were_put(tmp_path, src, std):

@@ -332,6 +332,14 @@ def test_frame_sharder_batching_cpu(workers, frames, batch):
     assert r.returncode == 0 and r.stdout.startswith("OK") and "batch_calls=0" not in r.stdout, r.stdout + r.stderr
 
 
+@pytest.mark.skipif(not os.path.exists(SHARDER_TEST), reason="oracle/_ref/ug_sharder_test not built")
+def test_option_tokenizer_corner_cases():
+    """mi355x::option_tokens, the one ':' tokenizer behind sharded_init and every tile init: "", "a", "a:b", "a::b", "a:" and ":a" give the token
+    lists the separate loops gave (empty tokens kept, for the callers to skip).  The expected lists are in module/ug_sharder_test.cpp.  No GPU."""
+    r = subprocess.run([SHARDER_TEST, "tokens"], capture_output=True, text=True, timeout=30)
+    assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
+
+
 @needs_harness
 def test_jpeg_module_registers():
     r = _run(["list"])

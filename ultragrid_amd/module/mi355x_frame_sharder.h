@@ -306,6 +306,18 @@ inline std::vector<int> parse_device_list(const char *s)
         return devs;
 }
 
+/// the ':'-separated tokens of an option string: "" -> none; "a::b" -> a, "", b and "a:" -> a, "" (the callers skip the empty ones)
+inline std::vector<std::string> option_tokens(const char *cfg)
+{
+        std::vector<std::string> tokens;
+        const std::string all = cfg ? cfg : "";
+        for (size_t pos = 0, end = 0; !all.empty() && end != std::string::npos; pos = end + 1) {
+                end = all.find(':', pos);
+                tokens.push_back(all.substr(pos, end == std::string::npos ? std::string::npos : end - pos));
+        }
+        return tokens;
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // Glue that turns a tile encoder (init / compress_tile / done, one state per tile and device, as the tile API of
 // video_compress.h:115-145 shapes it) into a module with the asynchronous frame API on top of frame_sharder.
@@ -335,17 +347,14 @@ inline void *sharded_init(struct module *parent, const char *cfg, tile_init_t ti
                           int (*set_device)(int), tile_compress_batch_t tile_compress_batch = nullptr, int (*bind_thread)(int device, int *cpus_bound) = nullptr,
                           int (*numa_node)(int device, int *node) = nullptr)
 {
-        std::string rest, all = cfg ? cfg : "";
+        std::string rest;
         std::vector<int> devices{ 0 };
         // Two workers per device by default: upload, kernels and download of consecutive frames overlap on one GPU (measured through
         // the reference framework over 4 000 4K frames: DXT5 1 979 -> 3 079 fps, JPEG 2 126 -> 2 393 fps, 8K v210 346 -> 445 fps); workers=1 gives the reference's one-per-device.
         int workers_per_device = 2;
         int batch = 1; // frames a busy worker may queue and then encode together ("batch=<n>"); 1 = the reference's one frame per worker
         bool numa = true; // workers run on the CPUs of their GPU's NUMA node ("numa=0": left to the scheduler, as the reference's workers are)
-        size_t pos = 0;
-        while (pos <= all.size() && !all.empty()) {
-                const size_t end = all.find(':', pos);
-                const std::string tok = all.substr(pos, end == std::string::npos ? std::string::npos : end - pos);
+        for (const std::string &tok : option_tokens(cfg)) {
                 if (tok == "help") { // usage text, INIT_NOERR; must work without a GPU
                         return tile_init(parent, "help");
                 }
@@ -361,8 +370,6 @@ inline void *sharded_init(struct module *parent, const char *cfg, tile_init_t ti
                 } else if (!tok.empty()) {
                         rest += (rest.empty() ? "" : ":") + tok;
                 }
-                if (end == std::string::npos) break;
-                pos = end + 1;
         }
         if (workers_per_device < 1 || workers_per_device > 8) {
                 log_msg(LOG_LEVEL_ERROR, "[MI355X] workers=<n> must be 1..8\n");

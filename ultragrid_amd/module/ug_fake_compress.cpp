@@ -1,8 +1,8 @@
 /**
  * @file ug_fake_compress.cpp
- * TEST-ONLY video_compress module "fake": the structure of vcompress_dxt_mi355x.cpp / vcompress_jpeg_mi355x.cpp -- per-tile encoder state with a
- * saved video_desc that reconfigures lazily on a format change (cuda_dxt.cpp:196-204), a batch entry, an output video_frame_pool, all of it behind
- * mi355x::sharded_init (workers=, batch=, dev=) and the asynchronous frame API -- with the GPU replaced by a hash, so that the run-time conventions
+ * TEST-ONLY video_compress module "fake": the skeleton of vcompress_dxt_mi355x.cpp / vcompress_jpeg_mi355x.cpp (mi355x_tile_encoder.h: the state core,
+ * the lazy reconfigure on a format change, the batch entry, the pool and the tail of a frame, behind mi355x::sharded_init with workers=, batch=, dev=
+ * and the asynchronous frame API), with the GPU replaced by a hash, so that the run-time conventions
  * of the boundary (format change in flight, CHANGE_COMPRESS, compress_done with frames queued) can be driven through the reference's framework on a
  * CPU box, under ThreadSanitizer and AddressSanitizer (tests/test_runtime_conventions.py).  Never part of the product: it is linked into
  * oracle/_ref/ug_runtime_harness_fake* only.
@@ -33,7 +33,7 @@
 #include "video_compress.h"
 #include "video_frame.h"
 
-#include "mi355x_frame_sharder.h"
+#include "mi355x_tile_encoder.h"
 
 #define MOD_NAME "[fake] "
 
@@ -43,42 +43,47 @@ constexpr size_t OUT_LEN = 80;
 std::atomic<uint32_t> g_state_serial{0};
 std::atomic<int> g_live_states{0}; // printed at exit: every init must have met its done
 
-struct state_fake {
-        struct video_desc saved_desc{};
+/// the device of this module: host memory, copies that are done when they return, no streams
+struct fake_device {
+        using stream_t = int;
+        using frame_allocator = default_data_allocator;
+        static int set_device(int d) { return d >= 0 && d < 64 ? 0 : -1; }
+        static int stream_create(stream_t *stream) { *stream = 1; return 0; }
+        static void stream_destroy(stream_t) {}
+        static int stream_sync(stream_t) { return 0; }
+        static int malloc(void **buf, size_t len) { return (*buf = ::malloc(len)) != nullptr ? 0 : -1; }
+        static void free(void *buf) { ::free(buf); }
+        static int download(int, void *dst, const void *src, size_t len, stream_t) { memcpy(dst, src, len); return 0; }
+        static const char *last_error() { return "no such fake device"; }
+};
+
+struct state_fake : mi355x::tile_encoder_state<fake_device> {
+        state_fake() : tile_encoder_state(MOD_NAME) {}
         struct video_desc cfg_desc{};
         uint32_t tag = 0;
         unsigned delay_us = 0, fail_every = 0;
-        int device = 0;
-        int batch_slices = 16;
         uint32_t serial = 0;
         uint64_t encoded = 0;
         std::mt19937 rng{1};
-        std::vector<char> dev_in; // stands for the device buffers: sized by configure_with(), so a stale size is an out-of-bounds write ASan sees
-        std::shared_ptr<video_frame_pool> pool = std::make_shared<video_frame_pool>(0, default_data_allocator()); ///< shared with the frames it gives out (mi355x::get_frame_keeping_pool)
+        void *dev_in = nullptr; // stands for the device buffers: sized by configure_with(), so a stale size is an out-of-bounds write ASan sees
 };
 
 void *fake_init(struct module *, const char *fmt)
 {
         auto *s = new state_fake();
-        std::string cfg = fmt ? fmt : "";
-        size_t pos = 0;
-        while (pos <= cfg.size() && !cfg.empty()) {
-                const size_t end = cfg.find(':', pos);
-                const std::string tok = cfg.substr(pos, end == std::string::npos ? std::string::npos : end - pos);
+        for (const std::string &tok : mi355x::option_tokens(fmt)) {
                 if (tok.rfind("tag=", 0) == 0) s->tag = (uint32_t) atoi(tok.c_str() + 4);
                 else if (tok.rfind("delay_us=", 0) == 0) s->delay_us = (unsigned) atoi(tok.c_str() + 9);
                 else if (tok.rfind("fail_every=", 0) == 0) s->fail_every = (unsigned) atoi(tok.c_str() + 11);
-                else if (tok.rfind("dev=", 0) == 0) s->device = atoi(tok.c_str() + 4);
-                else if (tok.rfind("batch_slices=", 0) == 0) s->batch_slices = atoi(tok.c_str() + 13);
+                else if (s->internal_option(tok)) continue;
                 else if (tok == "help") { printf("fake compress: test only\n"); delete s; return INIT_NOERR; }
                 else if (!tok.empty()) { MSG(ERROR, "unknown option: %s\n", tok.c_str()); delete s; return nullptr; }
-                if (end == std::string::npos) break;
-                pos = end + 1;
         }
         s->serial = g_state_serial++;
         s->rng.seed(s->serial * 7919u + 13u);
-        g_live_states++;
-        return s;
+        void *state = mi355x::opened(s);
+        if (state != nullptr) g_live_states++;
+        return state;
 }
 
 bool configure_with(state_fake *s, struct video_desc desc)
@@ -88,7 +93,7 @@ bool configure_with(state_fake *s, struct video_desc desc)
                 return false;
         }
         s->cfg_desc = desc;
-        s->dev_in.assign((size_t) vc_get_linesize(desc.width, desc.color_spec) * desc.height, 0);
+        if (s->buffers.get(&s->dev_in, (size_t) vc_get_linesize(desc.width, desc.color_spec) * desc.height) != 0) return false;
         struct video_desc out = desc;
         out.color_spec = DXT1;
         out.tile_count = 1;
@@ -108,57 +113,45 @@ std::shared_ptr<video_frame> encode_configured(state_fake *s, const std::shared_
         if (s->delay_us) std::this_thread::sleep_for(std::chrono::microseconds(s->rng() % (s->delay_us + 1)));
         s->encoded++;
         if (s->fail_every && s->encoded % s->fail_every == 0) return {};
-        memcpy(s->dev_in.data(), tx->tiles[0].data, tx->tiles[0].data_len); // the "upload": into the buffer the CONFIGURED geometry sized
-        std::shared_ptr<video_frame> out = mi355x::get_frame_keeping_pool(s->pool);
+        memcpy(s->dev_in, tx->tiles[0].data, tx->tiles[0].data_len); // the "upload": into the buffer the CONFIGURED geometry sized
         const struct video_desc d = video_desc_from_frame(tx.get());
         uint32_t rec[20] = { 0x454b4146u, s->tag, s->cfg_desc.width, s->cfg_desc.height, (uint32_t) s->cfg_desc.color_spec, (uint32_t) s->cfg_desc.interlacing,
                              d.width, d.height, (uint32_t) d.color_spec, (uint32_t) d.interlacing };
-        const uint64_t h = fnv1a(s->dev_in.data(), tx->tiles[0].data_len);
+        const uint64_t h = fnv1a((const char *) s->dev_in, tx->tiles[0].data_len);
         memcpy(&rec[10], &h, 8);
         rec[12] = batch_n; rec[13] = (uint32_t) s->device; rec[14] = tx->tiles[0].data_len; rec[15] = s->serial;
-        memcpy(out->tiles[0].data, rec, OUT_LEN);
-        out->tiles[0].data_len = OUT_LEN;
-        return out;
+        return mi355x::finished_frame(s, rec, OUT_LEN); // the "download" into a frame of the pool
 }
 
 std::shared_ptr<video_frame> fake_compress_tile(void *state, std::shared_ptr<video_frame> tx)
 {
         if (!tx) return {};
         auto *s = static_cast<state_fake *>(state);
-        if (!video_desc_eq_excl_param(video_desc_from_frame(tx.get()), s->saved_desc, PARAM_TILE_COUNT)) {
-                if (configure_with(s, video_desc_from_frame(tx.get()))) {
-                        s->saved_desc = video_desc_from_frame(tx.get());
-                } else {
-                        s->saved_desc = {};
-                        return {};
-                }
-        }
+        if (!mi355x::configured_for(s, tx.get(), configure_with)) return {};
         return encode_configured(s, tx, 1);
 }
 
-std::vector<std::shared_ptr<video_frame>> fake_compress_batch(void *state, std::vector<std::shared_ptr<video_frame>> in)
+bool no_batch_slices(state_fake *) { return true; }
+
+void encode_batch(state_fake *s, const mi355x::frames_t &in, mi355x::frames_t &out)
 {
-        auto *s = static_cast<state_fake *>(state);
-        std::vector<std::shared_ptr<video_frame>> out(in.size());
-        if (in.size() < 2 || (int) in.size() > s->batch_slices || !video_desc_eq_excl_param(video_desc_from_frame(in[0].get()), s->saved_desc, PARAM_TILE_COUNT)) {
-                for (size_t i = 0; i < in.size(); i++) out[i] = fake_compress_tile(state, std::move(in[i]));
-                return out;
-        }
         for (size_t i = 0; i < in.size(); i++) out[i] = encode_configured(s, in[i], (uint32_t) in.size());
-        return out;
+}
+
+mi355x::frames_t fake_compress_batch(void *state, mi355x::frames_t in)
+{
+        return mi355x::compress_batch(static_cast<state_fake *>(state), std::move(in), fake_compress_tile, no_batch_slices, encode_batch);
 }
 
 void fake_done(void *state)
 {
         g_live_states--;
-        delete static_cast<state_fake *>(state);
+        mi355x::tile_done<state_fake>(state);
 }
-
-int fake_set_device(int d) { return d >= 0 && d < 64 ? 0 : -1; }
 
 void *fake_module_init(struct module *parent, const char *cfg)
 {
-        return mi355x::sharded_init(parent, cfg, fake_init, fake_compress_tile, fake_done, fake_set_device, fake_compress_batch);
+        return mi355x::sharded_init(parent, cfg, fake_init, fake_compress_tile, fake_done, fake_device::set_device, fake_compress_batch);
 }
 
 compress_module_info get_fake_module_info()
@@ -168,9 +161,7 @@ compress_module_info get_fake_module_info()
         return mi;
 }
 
-const struct video_compress_info fake_info = {
-        fake_module_init, mi355x::sharded_done, NULL, NULL, mi355x::sharded_push, mi355x::sharded_pop, NULL, NULL, get_fake_module_info,
-};
+const struct video_compress_info fake_info = mi355x::sharded_compress_info(fake_module_init, get_fake_module_info);
 REGISTER_MODULE(fake, &fake_info, LIBRARY_CLASS_VIDEO_COMPRESS, VIDEO_COMPRESS_ABI_VERSION);
 
 struct report_at_exit {

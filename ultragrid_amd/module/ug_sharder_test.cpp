@@ -9,6 +9,7 @@
  * A round that holds a tiled frame is encoded one at a time, so in batch mode tiled frames are rare (every 40th, not every 5th) and every
  * worker's first call takes 30 ms: the producer fills the queues meanwhile and the first round a worker drains after it is a pure one --
  * that a batch forms does not depend on scheduling luck.
+ * ug_sharder_test tokens: mi355x::option_tokens, the one tokenizer of the option strings (sharded_init and every tile init), on the corner cases.
  */
 #include <atomic>
 #include <chrono>
@@ -23,8 +24,24 @@
 #include "mi355x_frame_sharder.h"
 #include "video_codec.h"
 
+/// what the ':' loops of sharded_init and of the tile inits yielded before they became option_tokens: empty tokens are kept (the callers skip them)
+static int test_option_tokens()
+{
+        const struct { const char *cfg; std::vector<std::string> tokens; } cases[] = {
+                { "", {} }, { "a", { "a" } }, { "a:b", { "a", "b" } }, { "a::b", { "a", "", "b" } }, { "a:", { "a", "" } }, { ":a", { "", "a" } },
+        };
+        int rc = 0;
+        for (const auto &c : cases) {
+                if (mi355x::option_tokens(c.cfg) != c.tokens) { fprintf(stderr, "option_tokens(\"%s\"): wrong tokens\n", c.cfg); rc = 1; }
+        }
+        if (!mi355x::option_tokens(nullptr).empty()) { fprintf(stderr, "option_tokens(NULL): tokens\n"); rc = 1; }
+        printf("%s option_tokens\n", rc ? "FAIL" : "OK");
+        return rc;
+}
+
 int main(int argc, char **argv)
 {
+        if (argc > 1 && strcmp(argv[1], "tokens") == 0) return test_option_tokens();
         const int workers = argc > 1 ? atoi(argv[1]) : 4;
         const unsigned frames = argc > 2 ? atoi(argv[2]) : 200;
         const unsigned batch = argc > 3 ? atoi(argv[3]) : 1;

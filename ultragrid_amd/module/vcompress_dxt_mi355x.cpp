@@ -27,7 +27,6 @@
  * codecs) is refused with the reference's message and the frame is dropped (video_compress.cpp:394-398 semantics).
  */
 #include <algorithm>
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -49,7 +48,7 @@
 
 #include "../../include/ug_mi355x.h"
 #include "ug_codec_map.h"
-#include "mi355x_frame_sharder.h"
+#include "mi355x_hip_device.h"
 
 #define MOD_NAME "[DXT MI355X] "
 
@@ -61,22 +60,8 @@
 
 namespace {
 
-/// pinned host memory for the compressed output frames (cuda_dxt.cpp:68-83 does the same with CUDA)
-struct hip_pinned_allocator : public video_frame_pool_allocator {
-        void *allocate(size_t size) override {
-                void *ptr = nullptr;
-                if (ug_hip_malloc_host(&ptr, size) != UG_HIP_SUCCESS) {
-                        return nullptr;
-                }
-                return ptr;
-        }
-        void deallocate(void *ptr) override { ug_hip_free_host(ptr); }
-        video_frame_pool_allocator *clone() const override { return new hip_pinned_allocator(*this); }
-};
-
-struct state_video_compress_dxt_mi355x {
-        struct video_desc saved_desc{};
-        int               device = 0;
+struct state_video_compress_dxt_mi355x : mi355x::tile_encoder_state<mi355x::hip_device> {
+        state_video_compress_dxt_mi355x() : tile_encoder_state(MOD_NAME) {}
         codec_t           out_codec = DXT1;
         ug_dxt_t          out_fmt = UG_DXT1;
         int               ties = UG_DXT_TIES_DEFAULT; ///< ties=even|away (include/ug_mi355x.h UG_DXT_TIES_*)
@@ -87,28 +72,12 @@ struct state_video_compress_dxt_mi355x {
         ug_pixfmt_t       in_fmt = UG_PF_NONE;      ///< format the encoder kernel reads
         ug_pixfmt_t       pre_in = UG_PF_NONE;      ///< != NONE: device-side conversion first (YUYV->UYVY, BGR->RGB, DXT1_YUV: anything->UYVY)
         ug_pixfmt_t       pre_out = UG_PF_NONE;     ///< its target format
-        ug_hip_stream_t   stream = nullptr;
         void             *dev_in = nullptr;         ///< uploaded frame, wire format
         void             *dev_pre = nullptr;        ///< swizzle result (only if pre_in != NONE)
         void             *dev_out = nullptr;        ///< DXT blocks
         size_t            in_len = 0, out_len = 0;
-        // the same buffers once per frame of a batch: allocated on first use, batch_slices slices (= the module's batch=<n>, handed down by
-        // the sharder as batch_slices=<n>; 16 if a caller hands batches to a state directly)
-        int               batch_slices = 16;
-        void             *b_in = nullptr, *b_pre = nullptr, *b_out = nullptr;
-        size_t            b_in_stride = 0, b_pre_stride = 0, b_out_stride = 0;
-        std::shared_ptr<video_frame_pool> pool = std::make_shared<video_frame_pool>(0, hip_pinned_allocator()); ///< shared with the frames it gives out (mi355x::get_frame_keeping_pool)
+        mi355x::slices    b_in, b_pre, b_out;       ///< the same buffers once per frame of a batch
 };
-
-void cleanup(state_video_compress_dxt_mi355x *s)
-{
-        for (void **p : { &s->dev_in, &s->dev_pre, &s->dev_out, &s->b_in, &s->b_pre, &s->b_out }) {
-                if (*p) {
-                        ug_hip_free(*p);
-                        *p = nullptr;
-                }
-        }
-}
 
 void usage()
 {
@@ -129,11 +98,7 @@ void *dxt_mi355x_compress_init(struct module *parent, const char *fmt)
 {
         (void) parent;
         auto *s = new state_video_compress_dxt_mi355x();
-        std::string cfg = fmt ? fmt : "";
-        size_t pos = 0;
-        while (pos <= cfg.size() && !cfg.empty()) {
-                size_t end = cfg.find(':', pos);
-                std::string tok = cfg.substr(pos, end == std::string::npos ? std::string::npos : end - pos);
+        for (const std::string &tok : mi355x::option_tokens(fmt)) {
                 if (strcasecmp(tok.c_str(), "DXT5") == 0) {
                         s->out_codec = DXT5;
                         s->out_fmt = UG_DXT5_YCOCG;
@@ -143,20 +108,7 @@ void *dxt_mi355x_compress_init(struct module *parent, const char *fmt)
                 } else if (strcasecmp(tok.c_str(), "DXT1_YUV") == 0) { // dxt_glsl.cpp:233-234
                         s->out_codec = DXT1_YUV;
                         s->out_fmt = UG_DXT1;
-                } else if (strncasecmp(tok.c_str(), "dev=", 4) == 0) {
-                        std::vector<int> devs;
-                        for (const char *p = tok.c_str() + 4; *p;) {
-                                devs.push_back(atoi(p));
-                                p = strchr(p, ',');
-                                if (!p) break;
-                                p++;
-                        }
-                        if (devs.empty()) devs.push_back(0);
-                        static std::atomic<unsigned> instance_counter{0}; // one init per tile: deal the instances out
-                        s->device = devs[instance_counter++ % devs.size()];
-                } else if (strncasecmp(tok.c_str(), "batch_slices=", 13) == 0) { // internal: from mi355x::sharded_init
-                        s->batch_slices = atoi(tok.c_str() + 13);
-                        if (s->batch_slices < 1 || s->batch_slices > 16) s->batch_slices = 16;
+                } else if (s->internal_option(tok)) { // (the list of dev=<n>[,<n>...] is dealt out by mi355x::sharded_init: this is one worker's device)
                 } else if (strncasecmp(tok.c_str(), "bands=", 6) == 0) {
                         s->bands = atoi(tok.c_str() + 6);
                         if (s->bands < 1 || s->bands > 16) {
@@ -181,22 +133,12 @@ void *dxt_mi355x_compress_init(struct module *parent, const char *fmt)
                         delete s;
                         return nullptr;
                 }
-                if (end == std::string::npos) {
-                        break;
-                }
-                pos = end + 1;
         }
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS || ug_hip_stream_create(&s->stream) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
-                delete s;
-                return nullptr;
-        }
-        return s;
+        return mi355x::opened(s);
 }
 
 bool configure_with(state_video_compress_dxt_mi355x *s, struct video_desc desc)
 {
-        cleanup(s);
         s->pre_in = s->pre_out = UG_PF_NONE;
         const ug_pixfmt_t wire = ug_pixfmt_from_codec(desc.color_spec);
         // The reference converts the wire format on the CPU to what get_best_decoder_from(codec, {RGB, UYVY}) ranks first
@@ -252,12 +194,12 @@ bool configure_with(state_video_compress_dxt_mi355x *s, struct video_desc desc)
         }
         s->in_len = (size_t) vc_get_linesize(desc.width, desc.color_spec) * desc.height;
         s->out_len = ug_hip_dxt_size(s->out_fmt, (int) desc.width, (int) desc.height);
-        CHECK_HIP(ug_hip_malloc(&s->dev_in, s->in_len + MAX_PADDING), "Could not allocate device input buffer", return false);
+        CHECK_HIP(s->buffers.get(&s->dev_in, s->in_len + MAX_PADDING), "Could not allocate device input buffer", return false);
         if (s->pre_in != UG_PF_NONE) {
                 const size_t pre_len = (size_t) vc_get_linesize(desc.width, ug_codec_from_pixfmt(s->pre_out)) * desc.height;
-                CHECK_HIP(ug_hip_malloc(&s->dev_pre, pre_len + MAX_PADDING), "Could not allocate device conversion buffer", return false);
+                CHECK_HIP(s->buffers.get(&s->dev_pre, pre_len + MAX_PADDING), "Could not allocate device conversion buffer", return false);
         }
-        CHECK_HIP(ug_hip_malloc(&s->dev_out, s->out_len), "Could not allocate device output buffer", return false);
+        CHECK_HIP(s->buffers.get(&s->dev_out, s->out_len), "Could not allocate device output buffer", return false);
 
         struct video_desc compressed_desc = desc;
         compressed_desc.color_spec = s->out_codec;
@@ -326,36 +268,21 @@ std::shared_ptr<video_frame> dxt_mi355x_compress_tile(void *state, std::shared_p
         auto *s = static_cast<state_video_compress_dxt_mi355x *>(state);
         CHECK_HIP(ug_hip_set_device(s->device), "set device", return {}); // tile callbacks run on pool threads
 
-        if (!video_desc_eq_excl_param(video_desc_from_frame(tx.get()), s->saved_desc, PARAM_TILE_COUNT)) {
-                if (configure_with(s, video_desc_from_frame(tx.get()))) {
-                        s->saved_desc = video_desc_from_frame(tx.get());
-                } else {
-                        MSG(ERROR, "Reconfiguration failed!\n");
-                        s->saved_desc = {};
-                        return {};
-                }
+        if (!mi355x::configured_for(s, tx.get(), configure_with)) {
+                return {};
         }
         const int w = (int) tx->tiles[0].width, h = (int) tx->tiles[0].height;
-
-        // Device-resident frame (mem_location == CUDA_MEM, types.h:295-298; the tile fan-out of video_compress.cpp drops that flag,
-        // so the pointer itself is asked as well): no upload -- the kernels read it in place (gpujpeg.cpp:617-622 does the same).
-        const void *enc_src = s->dev_in;
-        // In place only when the frame lives on THIS state's GPU: with dev=<list> / several workers a frame can be handed to a
-        // worker of another device, whose kernels must not dereference foreign memory -- that one is copied over (peer copy).
-        const bool blend_in_place = s->interlaced_input && s->pre_in == UG_PF_NONE; // the blend works in place: never on the caller's frame
-        if (!blend_in_place && ug_hip_pointer_device(tx->tiles[0].data) == s->device && ((uintptr_t) tx->tiles[0].data & 15) == 0) {
-                enc_src = tx->tiles[0].data;
-        } else {
-                const bool dev = tx->mem_location == CUDA_MEM || ug_hip_pointer_is_device(tx->tiles[0].data);
-                if (s->bands > 1 && !dev && !s->interlaced_input && h >= 32) { // (the blend runs down the whole frame: no bands there)
-                        return compress_tile_in_bands(s, tx, w, h);
-                }
-                CHECK_HIP(ug_hip_upload_ordered(s->device, s->dev_in, tx->tiles[0].data, s->in_len, dev ? UG_HIP_MEMCPY_DEVICE_TO_DEVICE : UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream),
-                          "upload failed", return {});
+        // a host frame in bands (a device-resident one is read in place or copied over whole; the blend runs down the whole frame: no bands there)
+        if (s->bands > 1 && !s->interlaced_input && h >= 32 && !mi355x::on_device<mi355x::hip_device>(*tx)) {
+                return compress_tile_in_bands(s, tx, w, h);
         }
-        const void *const wire_src = enc_src;
+        const bool blend_in_place = s->interlaced_input && s->pre_in == UG_PF_NONE; // the blend works in place: never on the caller's frame
+        const void *enc_src = mi355x::frame_source(s, *tx, s->dev_in, s->in_len, 16, !blend_in_place);
+        if (enc_src == nullptr) {
+                return {};
+        }
         if (s->pre_in != UG_PF_NONE) {
-                CHECK_HIP(ug_hip_pixfmt_convert(s->pre_in, s->pre_out, wire_src, s->dev_pre, w, h, 0, 0, 0, 8, 16, s->stream),
+                CHECK_HIP(ug_hip_pixfmt_convert(s->pre_in, s->pre_out, enc_src, s->dev_pre, w, h, 0, 0, 0, 8, 16, s->stream),
                           "device swizzle failed", return {});
                 enc_src = s->dev_pre;
         }
@@ -365,88 +292,55 @@ std::shared_ptr<video_frame> dxt_mi355x_compress_tile(void *state, std::shared_p
         }
         CHECK_HIP(ug_hip_dxt_encode_batch_ex(s->in_fmt, s->out_fmt, enc_src, s->dev_out, w, h, 0, 1, 0, 0, s->ties, s->stream),
                   "Encoding failed", return {});
+        return mi355x::finished_frame(s, s->dev_out, s->out_len);
+}
 
-        std::shared_ptr<video_frame> out = mi355x::get_frame_keeping_pool(s->pool);
-        CHECK_HIP(ug_hip_download_ordered(s->device, out->tiles[0].data, s->dev_out, s->out_len, s->stream), "D2H copy failed", return {});
-        CHECK_HIP(ug_hip_stream_sync(s->stream), "stream sync failed", return {});
-        out->tiles[0].data_len = (unsigned int) s->out_len;
-        return out;
+/// the buffers of one frame once per slice of a batch
+bool alloc_batch_slices(state_video_compress_dxt_mi355x *s)
+{
+        bool ok = s->batch_buffers.get(&s->b_in, s->in_len + MAX_PADDING, s->batch_slices) == UG_HIP_SUCCESS &&
+                  s->batch_buffers.get(&s->b_out, s->out_len, s->batch_slices) == UG_HIP_SUCCESS;
+        if (ok && s->pre_in != UG_PF_NONE) {
+                const size_t pre_len = (size_t) vc_get_linesize(s->saved_desc.width, ug_codec_from_pixfmt(s->pre_out)) * s->saved_desc.height;
+                ok = s->batch_buffers.get(&s->b_pre, pre_len + MAX_PADDING, s->batch_slices) == UG_HIP_SUCCESS;
+        }
+        return ok;
 }
 
 /// `frames` queued frames of one geometry: uploads (and device-side conversions) into the slices of the batch buffers, ONE encoder
 /// launch over all of them (ug_hip_dxt_encode_batch_ex, grid.z = frame), the downloads, one synchronisation.  Same bytes as one by one.
-std::vector<std::shared_ptr<video_frame>> dxt_mi355x_compress_batch(void *state, std::vector<std::shared_ptr<video_frame>> in)
+/// A failed download or synchronisation drops the whole batch.
+void encode_batch(state_video_compress_dxt_mi355x *s, const mi355x::frames_t &in, mi355x::frames_t &out)
 {
-        auto *s = static_cast<state_video_compress_dxt_mi355x *>(state);
-        const int n = (int) in.size();
-        std::vector<std::shared_ptr<video_frame>> out(in.size());
-        auto one_by_one = [&] {
-                for (size_t i = 0; i < in.size(); i++) out[i] = dxt_mi355x_compress_tile(state, std::move(in[i]));
-                return out;
-        };
-        if (n < 2 || n > s->batch_slices || ug_hip_set_device(s->device) != UG_HIP_SUCCESS ||
-            !video_desc_eq_excl_param(video_desc_from_frame(in[0].get()), s->saved_desc, PARAM_TILE_COUNT)) {
-                return one_by_one(); // (the first frame of a new geometry configures the state on the way)
-        }
-        const int w = (int) in[0]->tiles[0].width, h = (int) in[0]->tiles[0].height;
-        if (s->b_in == nullptr) {
-                auto round16 = [](size_t v) { return (v + 15) / 16 * 16; };
-                s->b_in_stride = round16(s->in_len + MAX_PADDING);
-                s->b_out_stride = round16(s->out_len);
-                bool ok = ug_hip_malloc(&s->b_in, s->b_in_stride * s->batch_slices) == UG_HIP_SUCCESS &&
-                          ug_hip_malloc(&s->b_out, s->b_out_stride * s->batch_slices) == UG_HIP_SUCCESS;
-                if (ok && s->pre_in != UG_PF_NONE) {
-                        s->b_pre_stride = round16((size_t) vc_get_linesize(w, ug_codec_from_pixfmt(s->pre_out)) * h + MAX_PADDING);
-                        ok = ug_hip_malloc(&s->b_pre, s->b_pre_stride * s->batch_slices) == UG_HIP_SUCCESS;
-                }
-                if (!ok) {
-                        MSG(WARNING, "no device memory for the batch buffers (%s): frames are encoded one by one\n", ug_hip_last_error_string());
-                        for (void **p : { &s->b_in, &s->b_pre, &s->b_out }) {
-                                if (*p) { ug_hip_free(*p); *p = nullptr; }
-                        }
-                        return one_by_one();
-                }
-        }
+        const int n = (int) in.size(), w = (int) in[0]->tiles[0].width, h = (int) in[0]->tiles[0].height;
         // all the uploads of the batch first, then the conversions: the upload lane of the device is shared by every worker, and an upload queued
         // behind this worker's conversion kernels would keep the other workers' uploads waiting with it
         for (int f = 0; f < n; f++) {
-                const bool dev = in[f]->mem_location == CUDA_MEM || ug_hip_pointer_is_device(in[f]->tiles[0].data);
-                char *slice = (char *) s->b_in + f * s->b_in_stride;
-                CHECK_HIP(ug_hip_upload_ordered(s->device, slice, in[f]->tiles[0].data, s->in_len, dev ? UG_HIP_MEMCPY_DEVICE_TO_DEVICE : UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream),
-                          "upload failed", return out);
+                if (!mi355x::upload_frame(s, *in[f], s->b_in[f], s->in_len)) return;
         }
         for (int f = 0; f < n && s->pre_in != UG_PF_NONE; f++) {
-                CHECK_HIP(ug_hip_pixfmt_convert(s->pre_in, s->pre_out, (char *) s->b_in + f * s->b_in_stride, (char *) s->b_pre + f * s->b_pre_stride, w, h, 0, 0, 0, 8, 16, s->stream),
-                          "device swizzle failed", return out);
+                CHECK_HIP(ug_hip_pixfmt_convert(s->pre_in, s->pre_out, s->b_in[f], s->b_pre[f], w, h, 0, 0, 0, 8, 16, s->stream), "device swizzle failed", return);
         }
-        const bool pre = s->pre_in != UG_PF_NONE;
+        const mi355x::slices &enc_in = s->pre_in != UG_PF_NONE ? s->b_pre : s->b_in;
         if (s->interlaced_input) {
-                CHECK_HIP(ug_hip_deinterlace_blend_batch(pre ? s->b_pre : s->b_in, (size_t) vc_get_linesize(w, ug_codec_from_pixfmt(s->target)), h, n,
-                                                         pre ? s->b_pre_stride : s->b_in_stride, s->stream),
-                          "de-interlacing failed", return out);
+                CHECK_HIP(ug_hip_deinterlace_blend_batch(enc_in.base, (size_t) vc_get_linesize(w, ug_codec_from_pixfmt(s->target)), h, n, enc_in.stride, s->stream),
+                          "de-interlacing failed", return);
         }
-        CHECK_HIP(ug_hip_dxt_encode_batch_ex(s->in_fmt, s->out_fmt, pre ? s->b_pre : s->b_in, s->b_out, w, h, 0, n, pre ? s->b_pre_stride : s->b_in_stride, s->b_out_stride,
-                                             s->ties, s->stream),
-                  "Encoding failed", return out);
+        CHECK_HIP(ug_hip_dxt_encode_batch_ex(s->in_fmt, s->out_fmt, enc_in.base, s->b_out.base, w, h, 0, n, enc_in.stride, s->b_out.stride, s->ties, s->stream),
+                  "Encoding failed", return);
         for (int f = 0; f < n; f++) {
-                out[f] = mi355x::get_frame_keeping_pool(s->pool);
-                CHECK_HIP(ug_hip_download_ordered(s->device, out[f]->tiles[0].data, (char *) s->b_out + f * s->b_out_stride, s->out_len, s->stream), "D2H copy failed",
-                          { for (auto &o : out) o.reset(); return out; });
-                out[f]->tiles[0].data_len = (unsigned int) s->out_len;
+                out[f] = mi355x::download_frame(s, s->b_out[f], s->out_len);
+                if (!out[f]) {
+                        for (auto &o : out) o.reset();
+                        return;
+                }
         }
-        CHECK_HIP(ug_hip_stream_sync(s->stream), "stream sync failed", { for (auto &o : out) o.reset(); return out; });
-        return out;
+        CHECK_HIP(ug_hip_stream_sync(s->stream), "stream sync failed", { for (auto &o : out) o.reset(); });
 }
 
-void dxt_mi355x_compress_done(void *state)
+mi355x::frames_t dxt_mi355x_compress_batch(void *state, mi355x::frames_t in)
 {
-        auto *s = static_cast<state_video_compress_dxt_mi355x *>(state);
-        ug_hip_set_device(s->device);
-        cleanup(s);
-        if (s->stream) {
-                ug_hip_stream_destroy(s->stream);
-        }
-        delete s;
+        return mi355x::compress_batch(static_cast<state_video_compress_dxt_mi355x *>(state), std::move(in), dxt_mi355x_compress_tile, alloc_batch_slices, encode_batch);
 }
 
 compress_module_info get_dxt_mi355x_module_info()
@@ -463,24 +357,9 @@ compress_module_info get_dxt_mi355x_module_info()
         return module_info;
 }
 
-/// module-level init: consumes dev=<list>, creates one worker (thread + per-tile encoder states) per listed device
-void *dxt_mi355x_module_init(struct module *parent, const char *cfg)
-{
-        return mi355x::sharded_init(parent, cfg, dxt_mi355x_compress_init, dxt_mi355x_compress_tile, dxt_mi355x_compress_done, ug_hip_set_device,
-                                    dxt_mi355x_compress_batch, ug_hip_bind_thread_to_device, ug_hip_device_numa_node);
-}
-
-const struct video_compress_info dxt_mi355x_info = {
-        dxt_mi355x_module_init,
-        mi355x::sharded_done,
-        NULL,
-        NULL,
-        mi355x::sharded_push, // asynchronous frame API: frames are dealt to one worker per listed GPU and popped in order
-        mi355x::sharded_pop,
-        NULL,
-        NULL,
-        get_dxt_mi355x_module_info,
-};
+const struct video_compress_info dxt_mi355x_info = mi355x::sharded_compress_info(
+        mi355x::hip_module_init<dxt_mi355x_compress_init, dxt_mi355x_compress_tile, mi355x::tile_done<state_video_compress_dxt_mi355x>, dxt_mi355x_compress_batch>,
+        get_dxt_mi355x_module_info);
 
 // "dxt" is a free name in the reference (it registers rtdxt, cuda_dxt, gpujpeg/jpeg)
 REGISTER_MODULE(dxt, &dxt_mi355x_info, LIBRARY_CLASS_VIDEO_COMPRESS, VIDEO_COMPRESS_ABI_VERSION);

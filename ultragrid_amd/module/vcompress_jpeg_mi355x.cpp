@@ -30,24 +30,16 @@
 
 #include "../../include/ug_mi355x.h"
 #include "ug_codec_map.h"
-#include "mi355x_frame_sharder.h"
+#include "mi355x_hip_device.h"
 
 #define MOD_NAME "[JPEG MI355X] "
 
 namespace {
 
-struct hip_pinned_allocator : public video_frame_pool_allocator {
-        void *allocate(size_t size) override {
-                void *ptr = nullptr;
-                return ug_hip_malloc_host(&ptr, size) == UG_HIP_SUCCESS ? ptr : nullptr;
-        }
-        void deallocate(void *ptr) override { ug_hip_free_host(ptr); }
-        video_frame_pool_allocator *clone() const override { return new hip_pinned_allocator(*this); }
-};
-
-struct state_video_compress_jpeg_mi355x {
-        struct video_desc    saved_desc{};
-        int                  device = 0, quality = 75, restart = 2;
+struct state_video_compress_jpeg_mi355x : mi355x::tile_encoder_state<mi355x::hip_device> {
+        state_video_compress_jpeg_mi355x() : tile_encoder_state(MOD_NAME) {}
+        ~state_video_compress_jpeg_mi355x() { if (enc) ug_hip_jpeg_encoder_destroy(enc); }
+        int                  quality = 75, restart = 2;
         int                  subsampling = 0;  ///< 0 = autoselect: that of the input codec (gpujpeg.cpp:168,295-302)
         int                  internal_cs = 0;  ///< color_space_internal asked for (gpujpeg.cpp:398-405): 0 = as the input dictates, else UG_JPEG_CS_RGB / _YCBCR_BT601 / _YCBCR_BT601_256LVLS / _YCBCR_BT709
         bool                 force_interleaved = false; ///< `:interleaved` (gpujpeg.cpp:396-397): RGB input as ONE scan instead of one scan per component
@@ -55,26 +47,11 @@ struct state_video_compress_jpeg_mi355x {
         ug_pixfmt_t          wire = UG_PF_NONE;     ///< format of the uploaded frame
         ug_pixfmt_t          target = UG_PF_NONE;   ///< what the reference's CPU line decoder would convert it to (UYVY, RGB or RGBA)
         ug_pixfmt_t          enc_in = UG_PF_NONE;   ///< what the encoder is fed: UYVY, RGB or I420
-        ug_hip_stream_t      stream = nullptr;
         ug_hip_jpeg_encoder *enc = nullptr;
         void                *dev_in = nullptr, *dev_target = nullptr, *dev_uyvy = nullptr, *dev_out = nullptr;
         size_t               in_len = 0, max_out = 0;
-        // the same buffers once per frame of a batch (batch=<n>): grown on first use
-        int                  batch_cap = 0;
-        int                  batch_slices = 16; // slices to allocate: the module's batch=<n>, handed down by the sharder as batch_slices=<n>
-        size_t               b_in_stride = 0, b_target_stride = 0, b_enc_stride = 0, b_out_stride = 0;
-        void                *b_in = nullptr, *b_target = nullptr, *b_enc = nullptr, *b_out = nullptr;
-        std::shared_ptr<video_frame_pool> pool = std::make_shared<video_frame_pool>(0, hip_pinned_allocator()); ///< shared with the frames it gives out (mi355x::get_frame_keeping_pool)
+        mi355x::slices       b_in, b_target, b_enc, b_out; ///< the same buffers once per frame of a batch (batch=<n>)
 };
-
-void cleanup(state_video_compress_jpeg_mi355x *s)
-{
-        if (s->enc) { ug_hip_jpeg_encoder_destroy(s->enc); s->enc = nullptr; }
-        for (void **p : { &s->dev_in, &s->dev_target, &s->dev_uyvy, &s->dev_out, &s->b_in, &s->b_target, &s->b_enc, &s->b_out }) {
-                if (*p) { ug_hip_free(*p); *p = nullptr; }
-        }
-        s->batch_cap = 0;
-}
 
 void usage()
 {
@@ -114,19 +91,11 @@ void *jpeg_mi355x_compress_init(struct module *parent, const char *fmt)
 {
         (void) parent;
         auto *s = new state_video_compress_jpeg_mi355x();
-        std::string cfg = fmt ? fmt : "";
-        size_t pos = 0;
         int numeric = 0;
-        while (!cfg.empty() && pos <= cfg.size()) {
-                size_t end = cfg.find(':', pos);
-                std::string tok = cfg.substr(pos, end == std::string::npos ? std::string::npos : end - pos);
+        for (const std::string &tok : mi355x::option_tokens(fmt)) {
                 if (!tok.empty() && isdigit((unsigned char) tok[0])) { // gpujpeg.cpp:379-391: "-c gpujpeg:<quality>[:<restart interval>]"
                         (numeric++ == 0 ? s->quality : s->restart) = atoi(tok.c_str());
-                } else if (strncasecmp(tok.c_str(), "dev=", 4) == 0) {
-                        s->device = atoi(tok.c_str() + 4);
-                } else if (strncasecmp(tok.c_str(), "batch_slices=", 13) == 0) { // internal: from mi355x::sharded_init
-                        s->batch_slices = atoi(tok.c_str() + 13);
-                        if (s->batch_slices < 1 || s->batch_slices > 16) s->batch_slices = 16;
+                } else if (s->internal_option(tok)) {
                 } else if (key_prefix(tok, "quality")) { // <k>=<v> with <k> any prefix of the key, as IS_KEY_PREFIX reads it (utils/macros.h:162-164; gpujpeg.cpp:392-395,406): q=, qual=, r=, sub= ...
                         s->quality = atoi(strchr(tok.c_str(), '=') + 1);
                 } else if (key_prefix(tok, "restart")) {
@@ -161,8 +130,6 @@ void *jpeg_mi355x_compress_init(struct module *parent, const char *fmt)
                         delete s;
                         return nullptr;
                 }
-                if (end == std::string::npos) break;
-                pos = end + 1;
         }
         if (s->subsampling != 0 && s->subsampling != 420 && s->subsampling != 422 && s->subsampling != 444) {
                 MSG(ERROR, "subsampling must be 444, 422 or 420\n");
@@ -174,17 +141,15 @@ void *jpeg_mi355x_compress_init(struct module *parent, const char *fmt)
                 delete s;
                 return nullptr;
         }
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS || ug_hip_stream_create(&s->stream) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
-                delete s;
-                return nullptr;
-        }
-        return s;
+        return mi355x::opened(s);
 }
 
 bool configure_with(state_video_compress_jpeg_mi355x *s, struct video_desc desc)
 {
-        cleanup(s);
+        if (s->enc) {
+                ug_hip_jpeg_encoder_destroy(s->enc);
+                s->enc = nullptr;
+        }
         s->wire = ug_pixfmt_from_codec(desc.color_spec);
         s->target = s->wire;
         // What the encoder is fed and which sampling it codes, as the reference decides it (gpujpeg.cpp:227-236,262-272,295-305,
@@ -268,13 +233,13 @@ bool configure_with(state_video_compress_jpeg_mi355x *s, struct video_desc desc)
         // Output capacity: the never-overflowing bound of the kernel library is ~10 B per pixel; a JPEG bigger than the raw RGB
         // frame only comes from noise at q=100, so the pooled (pinned) frames are sized for that and an overflow drops the frame.
         s->max_out = std::min(ug_hip_jpeg_encoder_max_size(s->enc), (size_t) desc.width * desc.height * 3 + 4096);
-        bool ok = ug_hip_malloc(&s->dev_in, s->in_len + MAX_PADDING) == UG_HIP_SUCCESS &&
-                  ug_hip_malloc(&s->dev_out, s->max_out) == UG_HIP_SUCCESS;
+        bool ok = s->buffers.get(&s->dev_in, s->in_len + MAX_PADDING) == UG_HIP_SUCCESS &&
+                  s->buffers.get(&s->dev_out, s->max_out) == UG_HIP_SUCCESS;
         if (ok && s->wire != s->target) { // staging buffer for the device-side decoder_t pass (wire -> target)
-                ok = ug_hip_malloc(&s->dev_target, (size_t) vc_get_linesize(desc.width, ug_codec_from_pixfmt(s->target)) * (desc.height + 1) + MAX_PADDING) == UG_HIP_SUCCESS;
+                ok = s->buffers.get(&s->dev_target, (size_t) vc_get_linesize(desc.width, ug_codec_from_pixfmt(s->target)) * (desc.height + 1) + MAX_PADDING) == UG_HIP_SUCCESS;
         }
         if (ok && s->target != s->enc_in) { // and for target -> encoder input (RGBA -> RGB; RGB-family -> UYVY on subsampling=422/420)
-                ok = ug_hip_malloc(&s->dev_uyvy, (size_t) vc_get_linesize(desc.width, s->enc_in == UG_PF_RGB ? RGB : UYVY) * desc.height + MAX_PADDING) == UG_HIP_SUCCESS;
+                ok = s->buffers.get(&s->dev_uyvy, (size_t) vc_get_linesize(desc.width, s->enc_in == UG_PF_RGB ? RGB : UYVY) * desc.height + MAX_PADDING) == UG_HIP_SUCCESS;
         }
         if (!ok) {
                 MSG(ERROR, "Could not allocate device buffers: %s\n", ug_hip_last_error_string());
@@ -296,24 +261,12 @@ std::shared_ptr<video_frame> jpeg_mi355x_compress_tile(void *state, std::shared_
         if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS) {
                 return {};
         }
-        if (!video_desc_eq_excl_param(video_desc_from_frame(tx.get()), s->saved_desc, PARAM_TILE_COUNT)) {
-                if (configure_with(s, video_desc_from_frame(tx.get()))) {
-                        s->saved_desc = video_desc_from_frame(tx.get());
-                } else {
-                        MSG(ERROR, "Reconfiguration failed!\n");
-                        s->saved_desc = {};
-                        return {};
-                }
+        if (!mi355x::configured_for(s, tx.get(), configure_with)) {
+                return {};
         }
         const int w = (int) tx->tiles[0].width, h = (int) tx->tiles[0].height;
-        // device-resident frame (types.h:295-298; gpujpeg.cpp:617-622): used in place, no upload -- when it lives on this state's GPU
-        const bool on_dev = tx->mem_location == CUDA_MEM || ug_hip_pointer_is_device(tx->tiles[0].data);
-        const void *enc_src = s->dev_in;
-        if (ug_hip_pointer_device(tx->tiles[0].data) == s->device && ((uintptr_t) tx->tiles[0].data & 15) == 0) {
-                enc_src = tx->tiles[0].data;
-        } else if (ug_hip_upload_ordered(s->device, s->dev_in, tx->tiles[0].data, s->in_len, on_dev ? UG_HIP_MEMCPY_DEVICE_TO_DEVICE : UG_HIP_MEMCPY_HOST_TO_DEVICE,
-                                         s->stream) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "upload failed: %s\n", ug_hip_last_error_string());
+        const void *enc_src = mi355x::frame_source(s, *tx, s->dev_in, s->in_len, 16);
+        if (enc_src == nullptr) {
                 return {};
         }
         if (s->wire != s->target) {
@@ -335,84 +288,51 @@ std::shared_ptr<video_frame> jpeg_mi355x_compress_tile(void *state, std::shared_
                 MSG(ERROR, "Encoding failed: %s\n", ug_hip_last_error_string());
                 return {};
         }
-        std::shared_ptr<video_frame> out = mi355x::get_frame_keeping_pool(s->pool);
-        if (ug_hip_download_ordered(s->device, out->tiles[0].data, s->dev_out, len, s->stream) != UG_HIP_SUCCESS ||
-            ug_hip_stream_sync(s->stream) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "D2H copy failed: %s\n", ug_hip_last_error_string());
-                return {};
+        return mi355x::finished_frame(s, s->dev_out, len, "D2H copy failed");
+}
+
+/// the buffers of one frame once per slice of a batch
+bool alloc_batch_slices(state_video_compress_jpeg_mi355x *s)
+{
+        const unsigned w = s->saved_desc.width, h = s->saved_desc.height;
+        const int n = s->batch_slices;
+        bool ok = s->batch_buffers.get(&s->b_in, s->in_len + MAX_PADDING, n) == UG_HIP_SUCCESS && s->batch_buffers.get(&s->b_out, s->max_out, n) == UG_HIP_SUCCESS;
+        if (ok && s->wire != s->target) {
+                ok = s->batch_buffers.get(&s->b_target, (size_t) vc_get_linesize(w, ug_codec_from_pixfmt(s->target == UG_PF_I420 ? UG_PF_UYVY : s->target)) * h + MAX_PADDING, n) == UG_HIP_SUCCESS;
         }
-        out->tiles[0].data_len = (unsigned int) len;
-        return out;
+        if (ok && s->target != s->enc_in) {
+                ok = s->batch_buffers.get(&s->b_enc, (size_t) vc_get_linesize(w, s->enc_in == UG_PF_RGB ? RGB : UYVY) * h + MAX_PADDING, n) == UG_HIP_SUCCESS;
+        }
+        return ok;
 }
 
 /// `frames` queued frames of one geometry in one go: per frame the upload (+ the device-side decoder_t passes) into its slice of the batch
 /// buffers, then ONE ug_hip_jpeg_encoder_encode_batch (fused front end grid.z = frame, entropy coder + compaction grid.y = frame, one
-/// synchronisation) and the downloads.  Streams are byte-identical to the one-frame path's.  Anything unusual -> the one-frame path.
-std::vector<std::shared_ptr<video_frame>> jpeg_mi355x_compress_batch(void *state, std::vector<std::shared_ptr<video_frame>> in)
+/// synchronisation) and the downloads.  Streams are byte-identical to the one-frame path's.  A stream that does not fit, or whose download
+/// fails, loses that frame only; a failed synchronisation loses the batch.
+void encode_batch(state_video_compress_jpeg_mi355x *s, const mi355x::frames_t &in, mi355x::frames_t &out)
 {
-        auto *s = static_cast<state_video_compress_jpeg_mi355x *>(state);
-        const int n = (int) in.size();
-        std::vector<std::shared_ptr<video_frame>> out(in.size());
-        auto one_by_one = [&] {
-                for (size_t i = 0; i < in.size(); i++) out[i] = jpeg_mi355x_compress_tile(state, std::move(in[i]));
-                return out;
-        };
-        if (n < 2 || n > s->batch_slices || ug_hip_set_device(s->device) != UG_HIP_SUCCESS) return one_by_one();
-        if (!video_desc_eq_excl_param(video_desc_from_frame(in[0].get()), s->saved_desc, PARAM_TILE_COUNT)) {
-                out[0] = jpeg_mi355x_compress_tile(state, in[0]); // (re)configures; the rest of this round follows one by one
-                for (size_t i = 1; i < in.size(); i++) out[i] = jpeg_mi355x_compress_tile(state, std::move(in[i]));
-                return out;
-        }
-        const int w = (int) in[0]->tiles[0].width, h = (int) in[0]->tiles[0].height;
-        if (n > s->batch_cap) {
-                for (void **p : { &s->b_in, &s->b_target, &s->b_enc, &s->b_out }) {
-                        if (*p) { ug_hip_free(*p); *p = nullptr; }
-                }
-                auto round16 = [](size_t v) { return (v + 15) / 16 * 16; };
-                s->b_in_stride = round16(s->in_len + MAX_PADDING);
-                s->b_target_stride = round16((size_t) vc_get_linesize(w, ug_codec_from_pixfmt(s->target == UG_PF_I420 ? UG_PF_UYVY : s->target)) * h + MAX_PADDING);
-                s->b_enc_stride = round16((size_t) vc_get_linesize(w, s->enc_in == UG_PF_RGB ? RGB : UYVY) * h + MAX_PADDING);
-                s->b_out_stride = round16(s->max_out);
-                const size_t slices = (size_t) s->batch_slices;
-                bool ok = ug_hip_malloc(&s->b_in, s->b_in_stride * slices) == UG_HIP_SUCCESS && ug_hip_malloc(&s->b_out, s->b_out_stride * slices) == UG_HIP_SUCCESS;
-                if (ok && s->wire != s->target) ok = ug_hip_malloc(&s->b_target, s->b_target_stride * slices) == UG_HIP_SUCCESS;
-                if (ok && s->target != s->enc_in) ok = ug_hip_malloc(&s->b_enc, s->b_enc_stride * slices) == UG_HIP_SUCCESS;
-                if (!ok) {
-                        MSG(WARNING, "no device memory for the batch buffers (%s): frames are encoded one by one\n", ug_hip_last_error_string());
-                        return one_by_one();
-                }
-                s->batch_cap = s->batch_slices;
-        }
+        const int n = (int) in.size(), w = (int) in[0]->tiles[0].width, h = (int) in[0]->tiles[0].height;
         // every frame into its slice: upload (or device-to-device), wire -> target -> encoder input with the pixfmt_conv.c arithmetic
-        const char *enc_base = (const char *) s->b_in;
-        size_t enc_stride = s->b_in_stride;
         // (all the uploads of the batch first, then the conversions: the device's upload lane is shared by every worker -- ADVICE r3)
         for (int f = 0; f < n; f++) {
-                const bool on_dev = in[f]->mem_location == CUDA_MEM || ug_hip_pointer_is_device(in[f]->tiles[0].data);
-                char *slice = (char *) s->b_in + f * s->b_in_stride;
-                if (ug_hip_upload_ordered(s->device, slice, in[f]->tiles[0].data, s->in_len, on_dev ? UG_HIP_MEMCPY_DEVICE_TO_DEVICE : UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream) != UG_HIP_SUCCESS) {
-                        MSG(ERROR, "upload failed: %s\n", ug_hip_last_error_string());
-                        return out;
-                }
+                if (!mi355x::upload_frame(s, *in[f], s->b_in[f], s->in_len)) return;
         }
         for (int f = 0; f < n; f++) {
-                const void *cur = (char *) s->b_in + f * s->b_in_stride;
+                const void *cur = s->b_in[f];
                 if (s->wire != s->target) {
-                        void *t = (char *) s->b_target + f * s->b_target_stride;
-                        if (wire_to_target(s, cur, t, w, h) != UG_HIP_SUCCESS) return out;
-                        cur = t;
+                        if (wire_to_target(s, cur, s->b_target[f], w, h) != UG_HIP_SUCCESS) return;
+                        cur = s->b_target[f];
                 }
                 if (s->target != s->enc_in) {
-                        void *t = (char *) s->b_enc + f * s->b_enc_stride;
-                        if (ug_hip_pixfmt_convert(s->target, s->enc_in, cur, t, w, h, 0, 0, 0, 8, 16, s->stream) != UG_HIP_SUCCESS) return out;
+                        if (ug_hip_pixfmt_convert(s->target, s->enc_in, cur, s->b_enc[f], w, h, 0, 0, 0, 8, 16, s->stream) != UG_HIP_SUCCESS) return;
                 }
         }
-        if (s->target != s->enc_in) { enc_base = (const char *) s->b_enc; enc_stride = s->b_enc_stride; }
-        else if (s->wire != s->target) { enc_base = (const char *) s->b_target; enc_stride = s->b_target_stride; }
+        const mi355x::slices &enc_in = s->target != s->enc_in ? s->b_enc : s->wire != s->target ? s->b_target : s->b_in;
         size_t lens[16] = {};
-        if (ug_hip_jpeg_encoder_encode_batch(s->enc, s->enc_in, n, enc_base, 0, enc_stride, s->b_out, s->b_out_stride, s->max_out, lens, s->stream) != UG_HIP_SUCCESS) {
+        if (ug_hip_jpeg_encoder_encode_batch(s->enc, s->enc_in, n, enc_in.base, 0, enc_in.stride, s->b_out.base, s->b_out.stride, s->max_out, lens, s->stream) != UG_HIP_SUCCESS) {
                 MSG(ERROR, "Encoding failed: %s\n", ug_hip_last_error_string());
-                return out;
+                return;
         }
         for (int f = 0; f < n; f++) {
                 if (lens[f] > s->max_out) { // only this frame is lost, as on the one-frame path
@@ -420,7 +340,7 @@ std::vector<std::shared_ptr<video_frame>> jpeg_mi355x_compress_batch(void *state
                         continue;
                 }
                 out[f] = mi355x::get_frame_keeping_pool(s->pool);
-                if (ug_hip_download_ordered(s->device, out[f]->tiles[0].data, (char *) s->b_out + f * s->b_out_stride, lens[f], s->stream) != UG_HIP_SUCCESS) {
+                if (ug_hip_download_ordered(s->device, out[f]->tiles[0].data, s->b_out[f], lens[f], s->stream) != UG_HIP_SUCCESS) {
                         out[f].reset();
                         continue;
                 }
@@ -430,16 +350,11 @@ std::vector<std::shared_ptr<video_frame>> jpeg_mi355x_compress_batch(void *state
                 MSG(ERROR, "D2H copy failed: %s\n", ug_hip_last_error_string());
                 for (auto &o : out) o.reset();
         }
-        return out;
 }
 
-void jpeg_mi355x_compress_done(void *state)
+mi355x::frames_t jpeg_mi355x_compress_batch(void *state, mi355x::frames_t in)
 {
-        auto *s = static_cast<state_video_compress_jpeg_mi355x *>(state);
-        ug_hip_set_device(s->device);
-        cleanup(s);
-        if (s->stream) ug_hip_stream_destroy(s->stream);
-        delete s;
+        return mi355x::compress_batch(static_cast<state_video_compress_jpeg_mi355x *>(state), std::move(in), jpeg_mi355x_compress_tile, alloc_batch_slices, encode_batch);
 }
 
 compress_module_info get_jpeg_mi355x_module_info()
@@ -457,24 +372,9 @@ compress_module_info get_jpeg_mi355x_module_info()
         return module_info;
 }
 
-/// module-level init: consumes dev=<list>, creates one worker (thread + per-tile encoder states) per listed device
-void *jpeg_mi355x_module_init(struct module *parent, const char *cfg)
-{
-        return mi355x::sharded_init(parent, cfg, jpeg_mi355x_compress_init, jpeg_mi355x_compress_tile, jpeg_mi355x_compress_done, ug_hip_set_device,
-                                    jpeg_mi355x_compress_batch, ug_hip_bind_thread_to_device, ug_hip_device_numa_node);
-}
-
-const struct video_compress_info jpeg_mi355x_info = {
-        jpeg_mi355x_module_init,
-        mi355x::sharded_done,
-        NULL,
-        NULL,
-        mi355x::sharded_push, // asynchronous frame API: frames are dealt to one worker per listed GPU and popped in order
-        mi355x::sharded_pop,
-        NULL,
-        NULL,
-        get_jpeg_mi355x_module_info,
-};
+const struct video_compress_info jpeg_mi355x_info = mi355x::sharded_compress_info(
+        mi355x::hip_module_init<jpeg_mi355x_compress_init, jpeg_mi355x_compress_tile, mi355x::tile_done<state_video_compress_jpeg_mi355x>, jpeg_mi355x_compress_batch>,
+        get_jpeg_mi355x_module_info);
 
 // Always reachable as "jpeg_mi355x".  The short name "jpeg" is the hidden alias the reference gives its GPUJPEG module
 // (gpujpeg.cpp:791-792, REGISTER_HIDDEN_MODULE(jpeg, ...)): in a build that contains that module (config.h: HAVE_GPUJPEG,

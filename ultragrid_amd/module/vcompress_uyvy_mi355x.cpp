@@ -31,7 +31,7 @@
 #include "video_frame.h"
 
 #include "../../include/ug_mi355x.h"
-#include "mi355x_frame_sharder.h"
+#include "mi355x_hip_device.h"
 
 #define MOD_NAME "[UYVY MI355X] "
 
@@ -43,39 +43,13 @@
 
 namespace {
 
-/// pinned host memory for the output frames
-struct hip_pinned_allocator : public video_frame_pool_allocator {
-        void *allocate(size_t size) override {
-                void *ptr = nullptr;
-                if (ug_hip_malloc_host(&ptr, size) != UG_HIP_SUCCESS) {
-                        return nullptr;
-                }
-                return ptr;
-        }
-        void deallocate(void *ptr) override { ug_hip_free_host(ptr); }
-        video_frame_pool_allocator *clone() const override { return new hip_pinned_allocator(*this); }
-};
-
-struct state_video_compress_uyvy_mi355x {
-        struct video_desc saved_desc{};
-        int               device = 0;
+struct state_video_compress_uyvy_mi355x : mi355x::tile_encoder_state<mi355x::hip_device> {
+        state_video_compress_uyvy_mi355x() : tile_encoder_state(MOD_NAME) {}
         ug_pixfmt_t       in_fmt = UG_PF_NONE;
-        ug_hip_stream_t   stream = nullptr;
         void             *dev_in = nullptr;  ///< uploaded frame
         void             *dev_out = nullptr; ///< UYVY
         size_t            in_len = 0, out_len = 0;
-        std::shared_ptr<video_frame_pool> pool = std::make_shared<video_frame_pool>(0, hip_pinned_allocator());
 };
-
-void cleanup(state_video_compress_uyvy_mi355x *s)
-{
-        for (void **p : { &s->dev_in, &s->dev_out }) {
-                if (*p) {
-                        ug_hip_free(*p);
-                        *p = nullptr;
-                }
-        }
-}
 
 void usage()
 {
@@ -88,14 +62,8 @@ void *uyvy_mi355x_compress_init(struct module *parent, const char *fmt)
 {
         (void) parent;
         auto *s = new state_video_compress_uyvy_mi355x();
-        std::string cfg = fmt ? fmt : "";
-        size_t pos = 0;
-        while (pos <= cfg.size() && !cfg.empty()) {
-                size_t end = cfg.find(':', pos);
-                std::string tok = cfg.substr(pos, end == std::string::npos ? std::string::npos : end - pos);
-                if (strncasecmp(tok.c_str(), "dev=", 4) == 0) { // (the sharder appends the worker's device)
-                        s->device = atoi(tok.c_str() + 4);
-                } else if (strncasecmp(tok.c_str(), "batch_slices=", 13) == 0) { // internal: from mi355x::sharded_init
+        for (const std::string &tok : mi355x::option_tokens(fmt)) {
+                if (s->internal_option(tok)) { // (the worker's device; batch_slices= is taken and not used: there is no batch entry)
                 } else if (tok == "help") {
                         usage();
                         delete s;
@@ -106,22 +74,12 @@ void *uyvy_mi355x_compress_init(struct module *parent, const char *fmt)
                         delete s;
                         return nullptr;
                 }
-                if (end == std::string::npos) {
-                        break;
-                }
-                pos = end + 1;
         }
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS || ug_hip_stream_create(&s->stream) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
-                delete s;
-                return nullptr;
-        }
-        return s;
+        return mi355x::opened(s);
 }
 
 bool configure_with(state_video_compress_uyvy_mi355x *s, struct video_desc desc)
 {
-        cleanup(s);
         switch (desc.color_spec) { // uyvy.cpp:158-168
         case RGB: s->in_fmt = UG_PF_RGB; break;
         case RGBA: s->in_fmt = UG_PF_RGBA; break;
@@ -131,8 +89,8 @@ bool configure_with(state_video_compress_uyvy_mi355x *s, struct video_desc desc)
         }
         s->in_len = (size_t) vc_get_linesize(desc.width, desc.color_spec) * desc.height;
         s->out_len = (size_t) vc_get_linesize(desc.width, UYVY) * desc.height;
-        CHECK_HIP(ug_hip_malloc(&s->dev_in, s->in_len + MAX_PADDING), "Could not allocate device input buffer", return false);
-        CHECK_HIP(ug_hip_malloc(&s->dev_out, s->out_len), "Could not allocate device output buffer", return false);
+        CHECK_HIP(s->buffers.get(&s->dev_in, s->in_len + MAX_PADDING), "Could not allocate device input buffer", return false);
+        CHECK_HIP(s->buffers.get(&s->dev_out, s->out_len), "Could not allocate device output buffer", return false);
         struct video_desc compressed_desc = desc;
         compressed_desc.color_spec = UYVY;
         compressed_desc.tile_count = 1;
@@ -148,43 +106,16 @@ std::shared_ptr<video_frame> uyvy_mi355x_compress_tile(void *state, std::shared_
         auto *s = static_cast<state_video_compress_uyvy_mi355x *>(state);
         CHECK_HIP(ug_hip_set_device(s->device), "set device", return {}); // tile callbacks run on pool threads
 
-        if (!video_desc_eq_excl_param(video_desc_from_frame(tx.get()), s->saved_desc, PARAM_TILE_COUNT)) {
-                if (configure_with(s, video_desc_from_frame(tx.get()))) {
-                        s->saved_desc = video_desc_from_frame(tx.get());
-                } else {
-                        MSG(ERROR, "Reconfiguration failed!\n");
-                        s->saved_desc = {};
-                        return {};
-                }
+        if (!mi355x::configured_for(s, tx.get(), configure_with)) {
+                return {};
         }
         const int w = (int) tx->tiles[0].width, h = (int) tx->tiles[0].height;
-        // device-resident frame on this state's GPU: converted in place (mem_location == CUDA_MEM, or the pointer itself asked: the tile
-        // fan-out of video_compress.cpp drops the flag); a frame of another device is copied over first
-        const void *src = s->dev_in;
-        if (ug_hip_pointer_device(tx->tiles[0].data) == s->device) {
-                src = tx->tiles[0].data;
-        } else {
-                const bool dev = tx->mem_location == CUDA_MEM || ug_hip_pointer_is_device(tx->tiles[0].data);
-                CHECK_HIP(ug_hip_upload_ordered(s->device, s->dev_in, tx->tiles[0].data, s->in_len, dev ? UG_HIP_MEMCPY_DEVICE_TO_DEVICE : UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream),
-                          "upload failed", return {});
+        const void *src = mi355x::frame_source(s, *tx, s->dev_in, s->in_len, 1); // (the converter takes any alignment)
+        if (src == nullptr) {
+                return {};
         }
         CHECK_HIP(ug_hip_pixfmt_convert(s->in_fmt, UG_PF_UYVY_GL, src, s->dev_out, w, h, 0, 0, 0, 8, 16, s->stream), "conversion failed", return {});
-        std::shared_ptr<video_frame> out = mi355x::get_frame_keeping_pool(s->pool);
-        CHECK_HIP(ug_hip_download_ordered(s->device, out->tiles[0].data, s->dev_out, s->out_len, s->stream), "D2H copy failed", return {});
-        CHECK_HIP(ug_hip_stream_sync(s->stream), "stream sync failed", return {});
-        out->tiles[0].data_len = (unsigned int) s->out_len;
-        return out;
-}
-
-void uyvy_mi355x_compress_done(void *state)
-{
-        auto *s = static_cast<state_video_compress_uyvy_mi355x *>(state);
-        ug_hip_set_device(s->device);
-        cleanup(s);
-        if (s->stream) {
-                ug_hip_stream_destroy(s->stream);
-        }
-        delete s;
+        return mi355x::finished_frame(s, s->dev_out, s->out_len);
 }
 
 compress_module_info get_uyvy_mi355x_module_info()
@@ -194,23 +125,8 @@ compress_module_info get_uyvy_mi355x_module_info()
         return module_info;
 }
 
-void *uyvy_mi355x_module_init(struct module *parent, const char *cfg)
-{
-        return mi355x::sharded_init(parent, cfg, uyvy_mi355x_compress_init, uyvy_mi355x_compress_tile, uyvy_mi355x_compress_done, ug_hip_set_device,
-                                    nullptr, ug_hip_bind_thread_to_device, ug_hip_device_numa_node);
-}
-
-const struct video_compress_info uyvy_mi355x_info = {
-        uyvy_mi355x_module_init,
-        mi355x::sharded_done,
-        NULL,
-        NULL,
-        mi355x::sharded_push,
-        mi355x::sharded_pop,
-        NULL,
-        NULL,
-        get_uyvy_mi355x_module_info,
-};
+const struct video_compress_info uyvy_mi355x_info = mi355x::sharded_compress_info(
+        mi355x::hip_module_init<uyvy_mi355x_compress_init, uyvy_mi355x_compress_tile, mi355x::tile_done<state_video_compress_uyvy_mi355x>>, get_uyvy_mi355x_module_info);
 
 REGISTER_MODULE(uyvy_mi355x, &uyvy_mi355x_info, LIBRARY_CLASS_VIDEO_COMPRESS, VIDEO_COMPRESS_ABI_VERSION);
 // The reference registers "uyvy" (uyvy.cpp:288) where configure found OpenGL; in such a build nothing of its registry changes and this module
