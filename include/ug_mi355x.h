@@ -412,6 +412,61 @@ struct ug_deinterlace_desc {
 int ug_hip_deinterlace(const struct ug_deinterlace_desc *d, ug_hip_stream_t stream);
 int ug_hip_deinterlace_supported(ug_pixfmt_t format, int mode); /* 1 / 0 */
 
+/* The per-pixel colour filters and the two mirror filters (`-F` capture filters, and `-p` postprocessors through capture_filter_wrapper.h) on
+ * device frames of `lines` lines of `width` pixels, byte for byte what the reference's C computes:
+ *   UG_PXF_MATRIX   src/capture_filter/matrix.c:127-309: out = M * pixel, a 3x3 double matrix on unpacked components.  UG_PF_UYVY comes out as
+ *                   UG_PF_RGB, 4 bytes -> 6, both pixels of a pair with the pair's U and V and the offsets -16 / -128 (:158-181); UG_PF_RGB and
+ *                   UG_PF_RG48 keep their format.  clamp != 0: `int val = ...; CLAMP(val, 0, 255)` -- 0..255 for RG48's 16-bit elements too (:217);
+ *                   clamp == 0 (`no-bound-check`, :95): the conversion below.
+ *   UG_PXF_MATRIX2  src/capture_filter/matrix2.c:167-243: the matrix on offset Y / Cb / Cr.  UG_PF_UYVY: chroma from y = (y1 + y2) / 2, luma
+ *                   from y1 and y2 (:174-196); UG_PF_Y416: offsets 1 << 15, 1 << 12, 1 << 15, alpha 0xFFFF (:219-237); UG_PF_V210: in one pass what
+ *                   the reference does in three, vc_copylineV210toY416 (pixfmt_conv.c:2834-2882), that loop, vc_copylineY416toV210 (:3004-3031).
+ *   UG_PXF_LUT      src/capture_filter/gamma.cpp:119-145: out[i] = lut[in[i]] per component; UG_PF_RGB (8 bits) or UG_PF_RG48 (16) in,
+ *                   out_format UG_PF_RGB or UG_PF_RG48 out; lut_dev = a device table of 256 or 65536 uint8_t or uint16_t (ug_hip_gamma_lut fills
+ *                   the host copy).  Every element is transformed (the reference's threads leave the last len % hardware_concurrency(), :133-138).
+ *   UG_PXF_GRAY     src/capture_filter/grayscale.c:95-102: UG_PF_UYVY with U = V = 127.
+ *   UG_PXF_MIRROR   src/capture_filter/mirror.c:76-93: a UG_PF_UYVY line reversed pair by pair, the two lumas of a pair swapped.
+ *   UG_PXF_FLIP     src/capture_filter/flip.c:96-99: line y -> line lines - 1 - y; every packed format (not UG_PF_I420, UG_PF_UYVY_GL).
+ * Arithmetic: integer -> double exact, IEEE fp64 products and sums in the reference's left-to-right order, never fused.  double -> integer: the
+ * reference converts straight to unsigned char / uint16_t, undefined outside that type's range; here it is truncation toward zero to int32 and
+ * then the low 8 or 16 bits, which is what its x86-64 build does.  So that the int32 step is defined, a matrix with a non-finite coefficient or a
+ * row with sum |m| * (65535 + 32768) >= 2^31 is refused (UG_HIP_EINVAL).
+ * A line is vc_get_linesize(format, width) bytes, all of it transformed (UYVY: whole pairs; v210: whole groups of the padded line -- the
+ * reference hands the decoder the whole frame as one line, matrix2.c:216, which is the same only for widths that are multiples of 48).  MATRIX
+ * on UYVY needs an even width.  out_format: UG_PF_NONE = the op's output format (MATRIX on UYVY: RGB; LUT: the input's), or that format named.
+ * Pitches 0 = the line size, otherwise at least that; pitches, strides and pointers multiples of the element (2 bytes: RG48, Y416; 4: v210;
+ * FLIP: 1); lines 1..65536, at most INT_MAX bytes per frame, frames 1..65535 (grid.z), frame i at src + i * src_frame_stride -> dst + i *
+ * dst_frame_stride.  Source and destination must not overlap, whatever the op.  An op / format pair without a kernel: UG_HIP_EUNSUPP; anything
+ * else: UG_HIP_EINVAL; both before any device call.  Units whose addresses are multiples of 16 take the dwordx4 path. */
+#define UG_PXF_MATRIX  0
+#define UG_PXF_MATRIX2 1
+#define UG_PXF_LUT     2
+#define UG_PXF_GRAY    3
+#define UG_PXF_MIRROR  4
+#define UG_PXF_FLIP    5
+struct ug_pixel_filter_desc {
+        const void *src;            /* device */
+        void       *dst;            /* device */
+        int         op;             /* UG_PXF_* */
+        ug_pixfmt_t format;
+        ug_pixfmt_t out_format;     /* UG_PF_NONE: the op's own */
+        int         width, lines;   /* pixels, lines */
+        size_t      src_pitch, dst_pitch;
+        int         frames;
+        size_t      src_frame_stride, dst_frame_stride;
+        double      matrix[9];      /* MATRIX, MATRIX2: row-major [a b c; d e f; g h i] */
+        int         clamp;          /* MATRIX: the bounds-checked form */
+        const void *lut_dev;        /* LUT: device table */
+};
+int ug_hip_pixel_filter(const struct ug_pixel_filter_desc *d, ug_hip_stream_t stream);
+int ug_hip_pixel_filter_supported(int op, ug_pixfmt_t format); /* 1 / 0 */
+/* The tables of `gamma` (gamma.cpp:74-93): table_host[i] = pow(i / max_in, gamma) * max_out converted to uint8_t (out_bits 8) or uint16_t (16),
+ * for i = 0 .. max_in, with the host's pow; in_bits and out_bits 8 or 16.  The caller uploads the table.  gamma <= 0 or not finite:
+ * UG_HIP_EINVAL (the reference warns, :170-172, and goes on to convert inf). */
+int ug_hip_gamma_lut(double gamma, int in_bits, int out_bits, void *table_host);
+/* matrix2's named matrices (matrix2.c:69-73,113): "y601_to_y709".  Unknown name: UG_HIP_EINVAL. */
+int ug_hip_matrix2_preset(const char *name, double m[9]);
+
 /* packed -> planar (to_planar.h:53-74) */
 int ug_hip_uyvy_to_i420(const void *src_dev, int src_pitch, void *y, int y_pitch, void *u, int u_pitch,
                         void *v, int v_pitch, int width, int height, ug_hip_stream_t stream); /* uyvy_to_i420, to_planar.c:343 */

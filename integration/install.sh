@@ -9,7 +9,7 @@ set -e
 UG=${1:?usage: install.sh <ultragrid-source-dir>}
 HERE=$(cd "$(dirname "$0")" && pwd); ROOT=$(dirname "$HERE"); M=$ROOT/ultragrid_amd/module
 test -f "$UG/configure.ac" || { echo "$UG: no configure.ac there" >&2; exit 1; }
-mkdir -p "$UG/include" "$UG/src/video_compress" "$UG/src/video_decompress" "$UG/src/libavcodec" "$UG/src/rtp" "$UG/src/vo_postprocess"
+mkdir -p "$UG/include" "$UG/src/video_compress" "$UG/src/video_decompress" "$UG/src/libavcodec" "$UG/src/rtp" "$UG/src/vo_postprocess" "$UG/src/capture_filter"
 cp "$ROOT/include/ug_mi355x.h"               "$UG/include/ug_mi355x.h"
 cp "$M/vcompress_dxt_mi355x.cpp"             "$UG/src/video_compress/dxt_mi355x.cpp"
 cp "$M/vcompress_jpeg_mi355x.cpp"            "$UG/src/video_compress/jpeg_mi355x.cpp"
@@ -25,9 +25,11 @@ cp "$M/mi355x_receiver.h"                    "$UG/src/rtp/"
 cp "$M/vo_pp_scale_mi355x.c"                "$UG/src/vo_postprocess/scale_mi355x.c"
 cp "$M/vo_pp_deinterlace_mi355x.c"          "$UG/src/vo_postprocess/deinterlace_mi355x.c"
 cp "$M/mi355x_receiver.h" "$M/ug_codec_map.h" "$UG/src/vo_postprocess/"
+cp "$M/capture_filter_pixel_mi355x.c"       "$UG/src/capture_filter/pixel_mi355x.c"
+cp "$M/mi355x_receiver.h" "$M/ug_codec_map.h" "$UG/src/capture_filter/"
 if grep -q "found_ug_mi355x" "$UG/configure.ac"; then
         echo "configure.ac is patched already"
 else
         patch -p1 -d "$UG" < "$HERE/ultragrid_mi355x.patch"
 fi
-echo "installed into $UG: 6 modules, the scale and de-interlacing postprocessors, the lavc hook and the ldgm_gpu library; configure with --with-ug-mi355x=<prefix>"
+echo "installed into $UG: 6 modules, the scale and de-interlacing postprocessors, the colour / mirror filters, the lavc hook and the ldgm_gpu library; configure with --with-ug-mi355x=<prefix>"

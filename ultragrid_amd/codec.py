@@ -146,6 +146,47 @@ def deinterlace(fmt: int, mode: int, src: torch.Tensor, linesize_bytes: int, lin
     return (dst[0], dst[1]) if two else dst[0]
 
 
+def gamma_lut(gamma: float, in_bits: int, out_bits: int) -> torch.Tensor:
+    """The host table of `gamma` (ug_hip_gamma_lut, gamma.cpp:74-93) as a CPU uint8 tensor of the table's bytes: 1 << in_bits entries of uint8_t (out_bits 8) or little-endian uint16_t (16)."""
+    buf = (C.c_uint8 * ((1 << in_bits) * (out_bits // 8)))()
+    L.check(L.load().ug_hip_gamma_lut(gamma, in_bits, out_bits, buf), "ug_hip_gamma_lut")
+    return torch.frombuffer(bytearray(buf), dtype=torch.uint8)
+
+
+def matrix2_preset(name: str) -> list:
+    m = (C.c_double * 9)()
+    L.check(L.load().ug_hip_matrix2_preset(name.encode(), m), "ug_hip_matrix2_preset")
+    return list(m)
+
+
+def pixel_filter(op: int, fmt: int, src: torch.Tensor, w: int, lines: int, matrix=None, clamp: bool = True, gamma: float | None = None,
+                 lut: torch.Tensor | None = None, out_fmt: int = L.PF_NONE, frames: int = 1, src_pitch: int = 0, dst_pitch: int = 0,
+                 dst: torch.Tensor | None = None) -> torch.Tensor:
+    """The reference's colour / mirror capture filters on the device (ug_hip_pixel_filter): op L.PXF_MATRIX (`matrix`; clamp False =
+    `no-bound-check`), L.PXF_MATRIX2, L.PXF_LUT (`gamma`: give `gamma`, or `lut` = the table's bytes; out_fmt PF_RGB / PF_RG48 = `:8` / `:16`),
+    L.PXF_GRAY, L.PXF_MIRROR, L.PXF_FLIP.  `frames` pictures of `lines` lines `src_pitch` (0: the line size) apart, back to back, in and out."""
+    src = _u8(src)
+    natural = L.PF_RGB if (op == L.PXF_MATRIX and fmt == L.PF_UYVY) else fmt
+    of = out_fmt or natural
+    sp, dp = src_pitch or linesize(fmt, w), dst_pitch or linesize(of, w)
+    if dst is None:
+        dst = torch.zeros(frames * dp * lines, dtype=torch.uint8, device=src.device)
+    dst = _u8(dst)
+    if src.numel() < frames * sp * lines or dst.numel() < frames * dp * lines:
+        raise ValueError("tensor smaller than the frames it should hold")
+    table = None
+    if op == L.PXF_LUT:
+        if lut is None:
+            if gamma is None:
+                raise ValueError("LUT needs gamma or a table")
+            lut = gamma_lut(gamma, 16 if fmt == L.PF_RG48 else 8, 16 if of == L.PF_RG48 else 8)
+        table = lut if lut.is_cuda else lut.to(src.device)
+    d = L.PixelFilterDesc(src.data_ptr(), dst.data_ptr(), op, fmt, out_fmt, w, lines, sp, dp, frames, sp * lines, dp * lines,
+                          (C.c_double * 9)(*(matrix if matrix is not None else [0.0] * 9)), int(clamp), table.data_ptr() if table is not None else None)
+    L.check(L.load().ug_hip_pixel_filter(C.byref(d), _stream()), "ug_hip_pixel_filter")
+    return dst
+
+
 def uyvy_to_i420(src: torch.Tensor, w: int, h: int):
     src = _u8(src)
     cw, ch = (w + 1) // 2, (h + 1) // 2

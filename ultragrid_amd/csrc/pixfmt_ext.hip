@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "ug_common.h"
+#include "v210_y416_device.h"
 
 namespace {
 
@@ -477,17 +478,13 @@ XK(k_y416_to_v210) // :3004-3029
         XPRO();
         if (x >= a.L / 16) return;
         const uint16_t *s = (const uint16_t *) srow + 24 * x;
-        uint32_t *d = (uint32_t *) drow + 4 * x;
-        uint32_t u[3], v[3], Y[6];
+        uint16_t t[24];
 #pragma unroll
-        for (int i = 0; i < 3; i++) {
-                u[i] = (uint16_t) ((s[8 * i] + s[8 * i + 4]) / 2), v[i] = (uint16_t) ((s[8 * i + 2] + s[8 * i + 6]) / 2);
-                Y[2 * i] = s[8 * i + 1], Y[2 * i + 1] = s[8 * i + 5];
-        }
-        d[0] = u[0] >> 6U | Y[0] >> 6U << 10U | v[0] >> 6U << 20U;
-        d[1] = Y[1] >> 6U | u[1] >> 6U << 10U | Y[2] >> 6U << 20U;
-        d[2] = v[1] >> 6U | Y[3] >> 6U << 10U | u[2] >> 6U << 20U;
-        d[3] = Y[4] >> 6U | v[2] >> 6U << 10U | Y[5] >> 6U << 20U;
+        for (int i = 0; i < 24; i++) t[i] = s[i];
+        uint32_t w[4];
+        ug::y416_pack_v210(t, w);
+        uint32_t *d = (uint32_t *) drow + 4 * x;
+        d[0] = w[0], d[1] = w[1], d[2] = w[2], d[3] = w[3];
 }
 
 // ---- 8-bit packed YUV <-> 16-bit packed YUV, VUYA -------------------------------------------------------------------------------------
@@ -587,8 +584,8 @@ __device__ __forceinline__ void k_v210_to_y2xx_body<Y416>::run(const XArgs &a, c
         if (x >= a.L / (Y416 ? 48 : 24)) return;
         const uint32_t *s = (const uint32_t *) srow + 4 * x;
         const uint32_t w0 = s[0], w1 = s[1], w2 = s[2], w3 = s[3];
-        const uint32_t Y[6] = { (w0 >> 10) & 0x3ff, w1 & 0x3ff, (w1 >> 20) & 0x3ff, (w2 >> 10) & 0x3ff, w3 & 0x3ff, (w3 >> 20) & 0x3ff };
-        const uint32_t U[3] = { w0 & 0x3ff, (w1 >> 10) & 0x3ff, (w2 >> 20) & 0x3ff }, V[3] = { (w0 >> 20) & 0x3ff, w2 & 0x3ff, (w3 >> 10) & 0x3ff };
+        uint32_t Y[6], U[3], V[3];
+        ug::v210_unpack(w0, w1, w2, w3, Y, U, V);
         if (Y416) {
                 uint16_t *d = (uint16_t *) drow + 24 * x;
 #pragma unroll

@@ -139,6 +139,10 @@ SYMBOLS = {
     "ug_hip_scale": (_i, [_vp, _vp]),
     "ug_hip_deinterlace": (_i, [_vp, _vp]),
     "ug_hip_deinterlace_supported": (_i, [_i, _i]),
+    "ug_hip_pixel_filter": (_i, [_vp, _vp]),
+    "ug_hip_pixel_filter_supported": (_i, [_i, _i]),
+    "ug_hip_gamma_lut": (_i, [C.c_double, _i, _i, _vp]),
+    "ug_hip_matrix2_preset": (_i, [C.c_char_p, C.POINTER(C.c_double)]),
 }
 
 
@@ -156,6 +160,16 @@ class DeinterlaceDesc(C.Structure):
     """struct ug_deinterlace_desc (include/ug_mi355x.h): ug_hip_deinterlace's frames and geometry"""
     _fields_ = [("src", _vp), ("prev", _vp), ("dst", _vp * 2), ("format", _i), ("mode", _i), ("blend_after_weave", _i), ("lines", _i),
                 ("linesize", _sz), ("src_pitch", _sz), ("dst_pitch", _sz), ("frames", _i), ("src_frame_stride", _sz), ("dst_frame_stride", _sz)]
+
+
+PXF_MATRIX, PXF_MATRIX2, PXF_LUT, PXF_GRAY, PXF_MIRROR, PXF_FLIP = range(6)
+
+
+class PixelFilterDesc(C.Structure):
+    """struct ug_pixel_filter_desc (include/ug_mi355x.h): ug_hip_pixel_filter's frames, geometry, matrix and table"""
+    _fields_ = [("src", _vp), ("dst", _vp), ("op", _i), ("format", _i), ("out_format", _i), ("width", _i), ("lines", _i),
+                ("src_pitch", _sz), ("dst_pitch", _sz), ("frames", _i), ("src_frame_stride", _sz), ("dst_frame_stride", _sz),
+                ("matrix", C.c_double * 9), ("clamp", _i), ("lut_dev", _vp)]
 
 
 class UgHipError(RuntimeError):
