@@ -252,6 +252,12 @@ int ug_hip_selftest_dxt_encode(unsigned *mismatches, ug_hip_stream_t stream);
  * reference's full form for all of its blocks.  Returns the number of such waves since the last reset on the current device:
  * [0] colour stage, [1] alpha stage.  Synchronises the device. */
 int ug_hip_dxt_encode_stats(unsigned long long full_form_waves[2], int reset);
+/* The same with a third count.  From a 4:2:2 source (UYVY, v210) the DXT5-YCoCg encoder takes the sign of SelectYCoCgDiagonal's
+ * covariance (glsl:169-183) from one product per chroma pair wherever an error bound decides it; a wave that holds a block the bound
+ * does not decide forms the reference's 16-term sum for all of its blocks.  counts[0 .. n - 1], n = 0 .. 3, receive
+ * { colour full form, alpha full form, waves that formed the reference's covariance sum }.  A reset through either function clears
+ * all three. */
+int ug_hip_dxt_encode_stats_ex(unsigned long long *counts, int n, int reset);
 /* Diagnostics (tests, profiling): what the last call of an LDGM session (below) issued -- kernel launches, host <-> device copies (the
  * schedule upload included) and levels of its decode schedule.  Any pointer may be NULL.  Does not touch the device. */
 typedef struct ug_hip_ldgm ug_hip_ldgm;

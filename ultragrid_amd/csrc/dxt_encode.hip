@@ -160,6 +160,12 @@ __device__ __forceinline__ uint32_t spread16(uint32_t x)
 #ifndef UG_DXT_BITS_INDEX
 #define UG_DXT_BITS_INDEX 1
 #endif
+// DXT5-YCoCg diagonal (SelectYCoCgDiagonal): with one chroma sample per pixel pair the SIGN of the covariance is taken from one product
+// per pair under an error certificate; a wave with an uncertified block forms the reference's 16-term sum (1 = on; 0 = the
+// reference's sum for every block; A/B switch).  Only loaders with kChromaPairs take it.
+#ifndef UG_DXT_PAIR_COV
+#define UG_DXT_PAIR_COV 1
+#endif
 [[maybe_unused]] constexpr float kIndexBias = 8388608.0f;      // 2^23
 [[maybe_unused]] constexpr uint32_t kIndexBits = 0x4b000000u;  // its bits: lowest set bit 24, so kIndexBits << 8 == 0 (mod 2^32) -- a row offset needs no correction
 // what `fields` accumulations acc = (acc << shift) + (kIndexBits + n) leave in a 32-bit word besides the n (wrap-around arithmetic)
@@ -177,8 +183,17 @@ __device__ __forceinline__ void count_full_form(int which)
                 atomicAdd(&g_full_form_waves[which], 1ull);
         }
 }
+// the same for the diagonal stage (ug_hip_dxt_encode_stats_ex): waves that formed the reference's covariance sum.  A counter of its own:
+// the two above keep meaning what they meant.
+__device__ unsigned long long g_exact_cov_waves;
+__device__ __forceinline__ void count_exact_cov()
+{
+        if ((int) threadIdx.x == __builtin_amdgcn_readfirstlane((int) threadIdx.x)) {
+                atomicAdd(&g_exact_cov_waves, 1ull);
+        }
+}
 struct IndexTables {
-        float *alpha;     // [8][64] floats: thresholds in DESCENDING order, row 7 = -inf
+        float *alpha;    // [8][64] floats: thresholds in DESCENDING order, row 7 = -inf
         float4 *colour;   // DXT5-YCoCg: [3][64] (A.x, A.y, B.x, B.y) of the palette pair whose bisector crosses zone k; DXT1: [6][64], rows 2k / 2k + 1 = A / B (xyz)
 };
 
@@ -594,7 +609,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
         }
 
         // SelectYCoCgDiagonal (glsl:169-183): sequential sum, i = 0..15
-        {
+        if constexpr (!(PAIRS && UG_DXT_PAIR_COV)) {
                 const float midx = (mxCo + mnCo) * 0.5f, midy = (mxCg + mnCg) * 0.5f;
                 float cov = 0.0f;
 #pragma unroll
@@ -603,6 +618,56 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         cov = cov + tx * ty;
                 }
                 if (cov < 0.0f) {
+                        const float t = mxCg; mxCg = mnCg; mnCg = t;
+                }
+        } else {
+                // One product per chroma pair (PAIRS, UG_DXT_PAIR_COV).  The reference uses cov for its SIGN only, so the sign is found
+                // from a cheaper sum and the reference's own sum is kept for the blocks where that one cannot tell.
+                //   rough = sum over the 8 EVEN pixels of tx ty, accumulated with fma: half of cov, up to the errors below.
+                // With hx = mxCo - mnCo, hy = mxCg - mnCg every |tx| <= hx / 2, |ty| <= hy / 2 (+ half an ulp of mid's own rounding, < 6e-8,
+                // which the slack at the end covers), so every product and every partial sum is bounded through hx hy / 4 per term.
+                //   Odd pixel replaced by its even one: the pixels of a pair differ by |dCo|, |dCg| < 5e-7 (the pair-location comment in the
+                //   colour stage; tests/test_dxt_pair_chroma_bound.py), and (tx + dx) (ty + dy) - tx ty = dx (ty + dy) + tx dy with the odd
+                //   pixel's own |ty + dy| <= hy / 2: <= 5e-7 (hx + hy) / 2 per pair, <= 2e-6 (hx + hy) over the eight.
+                //   The reference's roundings: 16 products of <= hx hy / 4 and 16 partial sums, the k-th <= k hx hy / 4, 2^-24 relative
+                //   each: (4 + 34) 2^-24 hx hy < 4e-6 hx hy.
+                //   The rough sum's roundings: 8 fma, the k-th partial sum <= k hx hy / 4: 9 * 2^-24 hx hy < 1e-6 hx hy, doubled with the sum.
+                // So |2 rough - cov| < 2e-6 (hx + hy) + 6e-6 hx hy, and the sign of rough is the sign of cov wherever
+                //   |2 rough| > eps = 1e-5 (hx + hy + hx hy):
+                // a factor > 2 over the analysis (tests/test_dxt_pair_cov_bound.py restates the stage in strict fp32 and finds
+                // |2 rough - cov| < 0.04 eps over its content).  The 2 is folded into the constant.  These fma only locate; no
+                // result of theirs is an operation of the reference.
+                // Exactly flat axis, hx hy == 0: with Co flat midx is mxCo itself (2 x * 0.5), every tx is exactly 0, the reference's
+                // cov is +-0 and it does not swap; with Cg flat the swap exchanges equal values.  rough is +-0 in both and rough < 0 is false:
+                // the same rule serves, and such blocks are certified without the comparison.
+                // A wave that holds a block the certificate does not cover (smooth content: one chroma sample under varying luma leaves
+                // spreads of rounding size) evaluates the reference's sum for all of its blocks and decides from it.
+                const float midx = (mxCo + mnCo) * 0.5f, midy = (mxCg + mnCg) * 0.5f;
+                const float hx = mxCo - mnCo, hy = mxCg - mnCg;
+                float rough = 0.0f;
+#pragma unroll
+                for (int i = 0; i < 16; i += 2) {
+                        rough = __builtin_fmaf(Co[i] - midx, Cg[i] - midy, rough);
+                }
+                const lanemask_t certain = LANEMASK(fabsf(rough) > 0.5e-5f * __builtin_fmaf(hx, hy, hx + hy)) | LANEMASK(hx * hy == 0.0f);
+                bool swap;
+                if (__builtin_expect(certain == LANEMASK(true), 1)) { // __all, on the two comparisons' own lane masks
+                        swap = rough < 0.0f;
+                } else {
+                        // The empty asm keeps this a real branch (see the alpha stage's fallback); the mids pass through it so that
+                        // this side forms its own differences: shared with the even pixels' above they would stay in registers up to here.
+                        float mx = midx, my = midy;
+                        asm volatile("; exact covariance" : "+v"(mx), "+v"(my) :: "memory");
+                        count_exact_cov();
+                        float cov = 0.0f;
+#pragma unroll
+                        for (int i = 0; i < 16; i++) {
+                                const float tx = Co[i] - mx, ty = Cg[i] - my;
+                                cov = cov + tx * ty;
+                        }
+                        swap = cov < 0.0f;
+                }
+                if (swap) {
                         const float t = mxCg; mxCg = mnCg; mnCg = t;
                 }
         }
@@ -1525,8 +1590,23 @@ extern "C" int ug_hip_dxt_encode_stats(unsigned long long full_form_waves[2], in
         if (reset) {
                 const unsigned long long zero[2] = { 0, 0 };
                 UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_full_form_waves), zero, sizeof zero));
+                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_cov_waves), zero, sizeof zero[0]));
         }
         return UG_HIP_SUCCESS;
+}
+
+// The same with the diagonal stage's counter: counts[0 .. n - 1] of { colour full form, alpha full form, exact covariance sum }
+extern "C" int ug_hip_dxt_encode_stats_ex(unsigned long long *counts, int n, int reset)
+{
+        if (n < 0 || n > 3 || (n > 0 && !counts)) return UG_HIP_EINVAL;
+        unsigned long long all[3] = { 0, 0, 0 };
+        UG_HIP_TRY(hipDeviceSynchronize());
+        if (n > 0) {
+                UG_HIP_TRY(hipMemcpyFromSymbol(all, HIP_SYMBOL(g_full_form_waves), 2 * sizeof all[0]));
+                UG_HIP_TRY(hipMemcpyFromSymbol(all + 2, HIP_SYMBOL(g_exact_cov_waves), sizeof all[0]));
+                for (int i = 0; i < n; i++) counts[i] = all[i];
+        }
+        return reset ? ug_hip_dxt_encode_stats(nullptr, 1) : UG_HIP_SUCCESS;
 }
 
 // Device self-test of the encoder's exact strength reductions (div14): *mismatches must come back 0.
