@@ -166,6 +166,12 @@ __device__ __forceinline__ uint32_t spread16(uint32_t x)
 #ifndef UG_DXT_PAIR_COV
 #define UG_DXT_PAIR_COV 1
 #endif
+// DXT5-YCoCg: products by a power of two, which are exact in binary32, ride inside the fma of the neighbouring sum, and the luma is kept
+// at 4 Y = r + 2 g + b through the alpha stage (1 = on; 0 = one instruction per product as the reference writes them; A/B switch).  The
+// argument is in encode_dxt5ycocg.
+#ifndef UG_DXT_POW2_FOLD
+#define UG_DXT_POW2_FOLD 1
+#endif
 [[maybe_unused]] constexpr float kIndexBias = 8388608.0f;      // 2^23
 [[maybe_unused]] constexpr uint32_t kIndexBits = 0x4b000000u;  // its bits: lowest set bit 24, so kIndexBits << 8 == 0 (mod 2^32) -- a row offset needs no correction
 // what `fields` accumulations acc = (acc << shift) + (kIndexBits + n) leave in a 32-bit word besides the n (wrap-around arithmetic)
@@ -589,15 +595,41 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
         //   (2r - 2b)*0.25 + off   : 2r-2b == 2(r-b) exactly, *0.25 exact -> (r-b)*0.5 + off,
         //                            and fma(r-b, 0.5, off) == ((r-b)*0.5) + off (product exact)
         //   (-r + 2g - b)*0.25+off : fma(g,2,-r) == -r + 2g ; fma(t,0.25,off) == t*0.25 + off
+        //
+        // The same rule through the rest of the function (UG_DXT_POW2_FOLD).  x * 2^k is exact unless it underflows, so
+        // RN(x * 2^k + c) == fma(x, 2^k, c) and RN(2^k x) == 2^k RN(x): wherever the reference multiplies by 2, 4, 8, 16, 1/2, 1/4, 1/16 or
+        // 1/32 and adds, the product moves into the fma of the sum, and the luma is never scaled at all: Y4 = r + 2 g + b = 4 Y is kept, and
+        // what it feeds is homogeneous of degree 1 (fmin / fmax commute with the scale, +, - and * by a constant scale with it), so the
+        // alpha stage compares Y4 <= 4 T where the reference compares Y <= T.  Sites, with the smallest non-zero magnitude the scaled
+        // operand takes (tests/test_dxt_pow2_fold_bound.py enumerates the first, and restates every site in strict fp32):
+        //   Y4 = t + b       the deleted * 0.25.  RGB front ends: r, g, b are bytes / 255, a non-zero r + 2 g + b is >= 1 / 255.  YUV front
+        //                    ends: r, g, b are sums of 1.1643 (y - 1/16) and products of (u | v) - 1/2 by constants of 0.2 .. 2.1, y, u, v
+        //                    bytes / 255.  y - 1/16 and u - 1/2 are 0 or multiples of the byte's last place, >= 2^-31 (a byte / 255 is
+        //                    >= 2^-8), and at least 2^-12 (|16 / 255 - 1/16|, |127.5 - 127| / 255) in magnitude, so every term is 0 or >= 2^-15
+        //                    with its last place >= 2^-39, and so is the last place of any sum of them: a non-zero t + b is >= 2^-39.
+        //                    The enumeration of every (y, u, v) finds 3 * 2^-28 at the least.
+        //   box ends         mnY + inset = fma(mn4, 1/4, inset) and inset = fma(mx4 - mn4, 1/128, -kInsetY): mx4 - mn4 = 4 (mxY - mnY)
+        //                    exactly, and / 128 of it is the reference's / 32.  The two ends leave the 4 x domain here, BEFORE the clamp
+        //                    and the * 255 rounding, through the fma they needed anyway (clamp modifier as before: no v_med3 to [0, 4],
+        //                    no 63.75, no instruction more than the reference's own inset: chosen over clamping in the 4 x domain, which
+        //                    costs two v_med3, at equal registers).  The thresholds go back up through their CONSTANTS: see there.
+        //   chroma ends      fma(mx - off, fs, off), fs = 1, 2, 4; insets fma(a - b, 1/16, -kInsetC); dequantised ends
+        //                    fma(x / 255 - off, rfs, off), rfs = 1, 1/2, 1/4.  Co, Cg and the end points are floats in (-2, 3) built from the
+        //                    terms above and off = 128 / 255, so multiples of 2^-39 again; mx - off, a - b and x / 255 - off are differences
+        //                    of two of them, or of one and a constant of that kind: equal, or >= 2^-39 apart (>= 2^-25 where both are near 1/2).
+        //   thresholds       (8 - k) mx + (k - 1) mn with one multiplier a power of two: that product inside the fma.
+        // No operand comes anywhere near 2^-124, below which a product by 1/32 would be denormal.  Overflow is out of the question
+        // (|values| < 16).  With -DUG_DXT_POW2_FOLD=0 every statement is the parent's.
+        constexpr bool kFold = UG_DXT_POW2_FOLD;
 #pragma unroll
         for (int i = 0; i < 16; i++) {
                 const float r = p.a[i], g = p.b[i], b = p.c[i];
                 const float t = __builtin_fmaf(g, 2.0f, r);
-                p.a[i] = (t + b) * 0.25f;
+                p.a[i] = kFold ? t + b : (t + b) * 0.25f; // kFold: Y4 = 4 Y
                 p.b[i] = __builtin_fmaf(r - b, 0.5f, kOffset);
                 p.c[i] = __builtin_fmaf(__builtin_fmaf(g, 2.0f, -r) - b, 0.25f, kOffset);
         }
-        float *Y = p.a, *Co = p.b, *Cg = p.c;
+        float *Y = p.a, *Co = p.b, *Cg = p.c; // kFold: Y[] holds Y4, and so do mnY / mxY up to InsetYBBox
 
         // FindMinMaxColorsBox (glsl:69-78)
         float mnY = Y[0], mxY = Y[0], mnCo = Co[0], mxCo = Co[0], mnCg = Cg[0], mxCg = Cg[0];
@@ -693,9 +725,9 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 uint32_t imax[2], imin[2];
 #pragma unroll
                 for (int k = 0; k < 2; k++) {
-                        float a = (mx_in[k] - kOffset) * fs + kOffset;
-                        float b = (mn_in[k] - kOffset) * fs + kOffset;
-                        const float inset = (a - b) * 0.0625f - kInsetC;
+                        float a = kFold ? __builtin_fmaf(mx_in[k] - kOffset, fs, kOffset) : (mx_in[k] - kOffset) * fs + kOffset;
+                        float b = kFold ? __builtin_fmaf(mn_in[k] - kOffset, fs, kOffset) : (mn_in[k] - kOffset) * fs + kOffset;
+                        const float inset = kFold ? __builtin_fmaf(a - b, 0.0625f, -kInsetC) : (a - b) * 0.0625f - kInsetC;
                         b = clamp01(b + inset);
                         a = clamp01(a - inset);
                         imax[k] = round_u32<AWAY>(a * q[k]);
@@ -710,13 +742,17 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 const float inv255 = (float) (1.0 / 255.0);
 #pragma unroll
                 for (int k = 0; k < 2; k++) {
-                        cmx[k] = ((float) imax[k] * inv255 - kOffset) * rfs + kOffset;
-                        cmn[k] = ((float) imin[k] * inv255 - kOffset) * rfs + kOffset;
+                        cmx[k] = kFold ? __builtin_fmaf((float) imax[k] * inv255 - kOffset, rfs, kOffset) : ((float) imax[k] * inv255 - kOffset) * rfs + kOffset;
+                        cmn[k] = kFold ? __builtin_fmaf((float) imin[k] * inv255 - kOffset, rfs, kOffset) : ((float) imin[k] * inv255 - kOffset) * rfs + kOffset;
                 }
         }
 
-        // InsetYBBox (glsl:86-91)
-        {
+        // InsetYBBox (glsl:86-91).  kFold: in come the ends of Y4, out go the reference's own ends (the site list at the top)
+        if constexpr (kFold) {
+                const float inset = __builtin_fmaf(mxY - mnY, 0.0078125f, -kInsetY);
+                mnY = clamp01(__builtin_fmaf(mnY, 0.25f, inset));
+                mxY = clamp01(__builtin_fmaf(mxY, 0.25f, -inset));
+        } else {
                 const float inset = (mxY - mnY) * 0.03125f - kInsetY;
                 mnY = clamp01(mnY + inset);
                 mxY = clamp01(mxY - inset);
@@ -739,11 +775,26 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         mid = range / 14.0f;
                 }
 #endif
+                // kFold: ab[k] = 4 x the reference's threshold, bit for bit, for the comparisons with Y4 below.  The ends, range and mid stay
+                // the reference's (so the range test, div14 and its route to the IEEE division are untouched: nothing here divides a
+                // scaled value); the 4 goes into the multipliers, RN(4 (8 - k) mx) = 4 RN((8 - k) mx), of which one per threshold is
+                // 4, 8 or 16 and rides in the fma of the sum; * inv7 scales with its operand, and + mid becomes fma(mid, 4, .).
+                // ab[1] = RN(4 mn + 4 mid) takes the one multiplication this form adds.
                 float ab[8];
-                ab[1] = mnY + mid;
+                if constexpr (kFold) {
+                        ab[1] = __builtin_fmaf(mid, 4.0f, mnY * 4.0f);
 #pragma unroll
-                for (int k = 2; k <= 7; k++) {
-                        ab[k] = ((float) (8 - k) * mxY + (float) (k - 1) * mnY) * inv7 + mid;
+                        for (int k = 2; k <= 7; k++) {
+                                const float cx_ = (float) (4 * (8 - k)), cn_ = (float) (4 * (k - 1));
+                                const float sum = k <= 3 || k == 5 ? __builtin_fmaf(mnY, cn_, cx_ * mxY) : __builtin_fmaf(mxY, cx_, cn_ * mnY);
+                                ab[k] = __builtin_fmaf(mid, 4.0f, sum * inv7);
+                        }
+                } else {
+                        ab[1] = mnY + mid;
+#pragma unroll
+                        for (int k = 2; k <= 7; k++) {
+                                ab[k] = ((float) (8 - k) * mxY + (float) (k - 1) * mnY) * inv7 + mid;
+                        }
                 }
                 // Thresholds in ascending order are T1..T7 = ab1, ab7, ab6, ab5, ab4, ab3, ab2 whenever they are
                 // monotone (always, except degenerate blocks whose clamped min == max).  For a monotone set the
@@ -794,11 +845,12 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         // The pattern kIndexBits + g' is used as it is: << 8 (the row offset) drops kIndexBits altogether, and the
                         // index words collect it as a known sum that is subtracted once per word (the true words are 30 and 18 bits).
                         const float inv = __builtin_amdgcn_rcpf(range);
-                        const float t0 = __builtin_fmaf(mnY, inv, (float) (6.5 / 7.0)), ninv = -inv;
+                        // kFold: t as before from the reference's ends; the pixels are Y4, so their factor takes the 1/4 (exact: the same t)
+                        const float t0 = __builtin_fmaf(mnY, inv, (float) (6.5 / 7.0)), ninv = kFold ? inv * -0.25f : -inv;
 #else
                         // t / 8 with the clamp modifier (luma of YUV sources can lie far outside [mnY, mxY]: g must stay in 0..7), then * (8 - ulp)
                         const float inv = 0.875f * __builtin_amdgcn_rcpf(range);
-                        const float t0 = __builtin_fmaf(mnY, inv, 0.875f), ninv = -inv;
+                        const float t0 = __builtin_fmaf(mnY, inv, 0.875f), ninv = kFold ? inv * -0.25f : -inv;
 #endif
                         constexpr int kA = UG_DXT5_ALPHA_GROUP;
 #pragma unroll
@@ -947,7 +999,8 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
 #if UG_DXT_BITS_INDEX
                         const float inv = 1.5f * __builtin_amdgcn_rcpf(vv);
                         const float ka = vx * inv, kb = vy * inv;
-                        const float kc = -(cx[0] * ka + cy[0] * kb) - 0.25f;
+                        // (kFold: kc locates only, so it may round twice instead of four times; s is then estimated no worse than above)
+                        const float kc = kFold ? __builtin_fmaf(-cx[0], ka, __builtin_fmaf(-cy[0], kb, -0.25f)) : -(cx[0] * ka + cy[0] * kb) - 0.25f;
 #else
                         const float inv = __builtin_amdgcn_rcpf(vv);
                         const float ka = vx * inv, kb = vy * inv;
