@@ -685,6 +685,12 @@ int    ug_hip_jpeg_colour_convert(ug_pixfmt_t fmt, int cs_in, int cs_out, const 
                                   ug_hip_stream_t stream);
 void   ug_hip_jpeg_encoder_destroy(ug_hip_jpeg_encoder *enc);
 size_t ug_hip_jpeg_encoder_max_size(const ug_hip_jpeg_encoder *enc);
+/* Pitch and alignment of the source (encode and encode_batch alike, whatever kernels the restart interval, the size and the alignment
+ * select): src_pitch 0 = packed, else at least the line (UG_PF_UYVY: ug_hip_linesize, UG_PF_RGB 3, UG_PF_RGBA 4 bytes per pixel).
+ * UG_PF_UYVY and UG_PF_RGBA are lines of 32-bit words: src_dev, src_pitch and, with frames > 1, src_stride are multiples of 4 (multiples
+ * of 16, with a width that is one, take the 128-bit loads).  UG_PF_RGB: any pitch from the line size up and any address.  UG_PF_I420 is
+ * tightly packed: src_pitch 0 or the width.  Only the width x height pixels are read as pixels: blocks that reach past the picture repeat
+ * its last column / row, never the line padding.  Anything else is UG_HIP_EINVAL, before any device work, and nothing is written. */
 int    ug_hip_jpeg_encoder_encode(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, const void *src_dev, int src_pitch,
                                   void *out_dev, size_t out_capacity, size_t *out_len, ug_hip_stream_t stream);
 /* `frames` (1..16) frames of the same geometry in ONE call: one launch sequence over all of them (UYVY / RGB input: ONE kernel does the
@@ -730,7 +736,14 @@ int    ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in
  * (ug_hip_jpeg_decoder_plane).  Not a baseline stream / unsupported layout (incl. a second frame header, or a table redefined between
  * the scans of a one-scan-per-component stream): UG_HIP_EUNSUPP.  Damage inside the entropy-coded data is not
  * an error: a segment ends at its first marker, a missing one decodes as an empty one (what a sequential decoder does).  A decoder object
- * holds the work buffers of one frame in flight: one object per thread / per frame in flight. */
+ * holds the work buffers of one frame in flight: one object per thread / per frame in flight.
+ * Pitch and alignment of the destination: dst_pitch 0 = packed, else at least the line of `out` (ug_hip_linesize).  UG_PF_UYVY and
+ * UG_PF_RGBA from the streams with kernels of their own -- Y'CbCr 4:4:4 / 4:2:2 / 4:2:0 at their usual factors, R,G,B(,A) 4:4:4, greyscale
+ * -- leave as 32-bit words: dst_dev and dst_pitch are multiples of 4, for every one of these streams alike.  UG_PF_RGB: any pitch from the
+ * line size up and any address, and so every output of the other sampling layouts (layout_pack_kernel picks its store width from the
+ * address).  UG_PF_I420 is tightly packed: dst_pitch 0 or the width.  Only the pixels of the picture are written: line padding and whatever
+ * follows the last line stay as they were.  Anything else is UG_HIP_EINVAL, after the header parse and before any device work: nothing is
+ * written, and the decoder object takes the next call as if this one had not been made. */
 typedef struct ug_hip_jpeg_decoder ug_hip_jpeg_decoder;
 int  ug_hip_jpeg_decoder_create(ug_hip_jpeg_decoder **out);
 void ug_hip_jpeg_decoder_destroy(ug_hip_jpeg_decoder *dec);

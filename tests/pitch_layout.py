@@ -1,7 +1,8 @@
 """Pitched and offset buffers for the tests of the pitch / alignment arguments of the C ABI (ug_hip_pixfmt_convert[_batch],
 ug_hip_dxt_decode): the layouts, the reference conversion run line by line on the very same pitched bytes, and the byte-for-byte
-comparison with canaries in front of the buffer, behind it and in the padding of every line.  Plain numpy + ctypes, no GPU: the helper's
-own checks are tests/test_pitch_layout.py."""
+comparison with canaries in front of the buffer, behind it and in the padding of every line; and, for the JPEG encoder and decoder
+(tests/test_gpu_jpeg_pitch.py, tests/test_gpu_jpeg_decode_pitch.py), the source side: packed frames placed at a pitch, an offset and a frame
+stride among random bytes (place_frames).  Plain numpy + ctypes, no GPU: the helper's own checks are tests/test_pitch_layout.py."""
 import ctypes as C
 import json
 import os
@@ -143,6 +144,35 @@ def aligned_bytes(n, fill=None, rng=None):
 def make_src(h, src_pitch, src_off, rng):
     """random bytes everywhere: the lines, their padding and what follows the picture"""
     return aligned_bytes(src_off + src_pitch * h + SLACK, rng=rng)
+
+
+def frame_mask(frames, line, h, pitch, off, stride, size):
+    """the bytes of a buffer of `size` bytes that belong to the lines of `frames` pictures (place_frames): a bool array"""
+    inside = np.zeros(size, bool)
+    at = off + (np.arange(frames)[:, None, None] * stride + np.arange(h)[None, :, None] * pitch + np.arange(line)[None, None, :])
+    inside[at.ravel()] = True
+    return inside
+
+
+def place_frames(frames_packed, line, h, pitch, off, stride, rng):
+    """Source side: the packed frames (each h lines of `line` bytes) laid out `stride` bytes apart at `pitch` bytes per line, the first one `off`
+    bytes into a 256-byte aligned buffer.  Every other byte is random (rng.bytes): the `off` bytes in front, the padding of every line, the gaps
+    between the frames and SLACK bytes behind the last line -- a kernel that reads padding as pixels, or replicates an edge from the padding
+    instead of the last pixel, computes something else."""
+    n = len(frames_packed)
+    assert pitch >= line and (n == 1 or stride >= pitch * h)
+    buf = aligned_bytes(off + (n - 1) * stride + pitch * h + SLACK, rng=rng)
+    for f, frame in enumerate(frames_packed):
+        rows = np.asarray(frame, np.uint8).reshape(-1)[: line * h].reshape(h, line)
+        for y in range(h):
+            at = off + f * stride + y * pitch
+            buf[at: at + line] = rows[y]
+    return buf
+
+
+def extract_frames(buf, frames, line, h, pitch, off, stride):
+    """the packed frames back out of a buffer place_frames made"""
+    return [np.stack([buf[off + f * stride + y * pitch: off + f * stride + y * pitch + line] for y in range(h)]).ravel() for f in range(frames)]
 
 
 def make_dst(h, dst_pitch, dst_off):

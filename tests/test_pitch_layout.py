@@ -162,3 +162,40 @@ def test_restated_pitched_reference_equals_the_compiled_one(po):
                         lines = lambda v: v[front: front + dp * h].reshape(h, dp)[:, : sz.written_len]  # noqa: E731
                         assert np.array_equal(lines(a), lines(other)), (i, o, w, name, sh)
                         assert (other[:front] == pl.FILL).all()   # (behind dst_len both write whole last groups: compare() never reads that)
+
+
+class _Const:
+    """an `rng` whose bytes are all one value: two of them differ in every byte they supply"""
+
+    def __init__(self, v):
+        self.v = v
+
+    def bytes(self, n):
+        return bytes([self.v]) * n
+
+
+@pytest.mark.parametrize("line,h,pitch,off,stride,n", [(72, 5, 72, 0, 72 * 5, 1), (72, 5, 112, 0, 112 * 5 + 80, 3), (1044, 9, 1048, 4, 1048 * 9 + 12, 3),
+                                                       (144, 16, 157, 1, 157 * 16 + 12, 3)])
+def test_place_frames(line, h, pitch, off, stride, n):
+    """extraction gives the frames back; every byte outside the lines comes from the rng (it differs between two rngs that differ everywhere, and
+    between two seeds wherever two random bytes differ: all but about one in 256), every byte inside from the frames; the buffer is 256-byte aligned
+    and ends SLACK bytes behind the last line"""
+    frames = [np.random.default_rng(10 + f).integers(0, 256, line * h, dtype=np.uint8) for f in range(n)]
+    a = pl.place_frames(frames, line, h, pitch, off, stride, _Const(0x11))
+    b = pl.place_frames(frames, line, h, pitch, off, stride, _Const(0x22))
+    assert a.ctypes.data % 256 == 0 and a.size == b.size == off + (n - 1) * stride + pitch * h + pl.SLACK
+    for buf in (a, b):
+        back = pl.extract_frames(buf, n, line, h, pitch, off, stride)
+        assert all(np.array_equal(x, y) for x, y in zip(back, frames))
+    inside = pl.frame_mask(n, line, h, pitch, off, stride, a.size)
+    assert inside.sum() == n * h * line
+    assert (a[~inside] == 0x11).all() and (b[~inside] == 0x22).all() and np.array_equal(a[inside], b[inside])
+    c = pl.place_frames(frames, line, h, pitch, off, stride, np.random.default_rng(1))
+    d = pl.place_frames(frames, line, h, pitch, off, stride, np.random.default_rng(2))
+    assert np.array_equal(c[inside], d[inside]) and np.array_equal(c[inside], a[inside])
+    outside = int((~inside).sum())
+    assert outside >= pl.SLACK + off
+    # two independent uniform bytes coincide with probability 1 / 256: over `outside` bytes more than 1 / 256 + 5 sigma of them would be no chance
+    same = int((c[~inside] == d[~inside]).sum())
+    assert same <= outside / 256 + 5 * (outside / 256) ** 0.5, (same, outside)
+    assert len(set(c[~inside].tolist())) > 64   # random, not a constant

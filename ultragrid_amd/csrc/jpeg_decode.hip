@@ -1379,6 +1379,21 @@ int ug_hip_jpeg_decoder_decode_sized(ug_hip_jpeg_decoder *dec, const void *jpeg_
                 ug::set_last_error_msg("ug_hip_jpeg_decoder_decode: the stream's picture size is not the size the destination was made for");
                 return UG_HIP_EINVAL;
         }
+        // the destination's pitch and alignment (ug_mi355x.h), before any device work: the output kernels of the classic layouts store UYVY and
+        // RGBA as 32-bit words; layout_pack_kernel picks its store width from the address
+        if (out == UG_PF_I420) {
+                if (dst_pitch && dst_pitch != h.width) {
+                        ug::set_last_error_msg("ug_hip_jpeg_decoder_decode: I420 output is tightly packed (dst_pitch 0 or the width)");
+                        return UG_HIP_EINVAL;
+                }
+        } else if (out == UG_PF_UYVY || out == UG_PF_RGB || out == UG_PF_RGBA) {
+                const bool words = out != UG_PF_RGB && classic_layout(h);
+                if ((dst_pitch && dst_pitch < ug::linesize(out, h.width)) || (words && ((dst_pitch & 3) || (3 & (uintptr_t) dst_dev)))) {
+                        ug::set_last_error_msg("ug_hip_jpeg_decoder_decode: dst_pitch must be 0 or at least the line size; UYVY and RGBA: dst_dev and dst_pitch "
+                                               "multiples of 4 (4:4:4 / 4:2:2 / 4:2:0, R,G,B(,A) 4:4:4 and greyscale streams)");
+                        return UG_HIP_EINVAL;
+                }
+        }
         // (the sampling layouts were checked by parse(): every one it takes has an output path below)
         hipStream_t st = (hipStream_t) stream;
         // ---- workspace ----
@@ -1648,6 +1663,9 @@ int ug_hip_jpeg_decoder_decode_sized(ug_hip_jpeg_decoder *dec, const void *jpeg_
                 }
                 if (out == UG_PF_UYVY) { // through packed RGB and vc_copylineRGBtoUYVY's arithmetic
                         if (!need_tmp(UG_PF_RGB)) return UG_HIP_ERUNTIME;
+                        // an odd width: the last pair of a line takes its second pixel from what follows the line (vc_copylineRGBtoUYVY) -- the next
+                        // line's first pixel, and behind the last line zeros, as behind a frame the reference converts (need_tmp leaves 64 bytes there)
+                        if (w & 1) UG_HIP_TRY(hipMemsetAsync(d->tmp + (size_t) 3 * w * hh, 0, 64, st));
                         hipLaunchKernelGGL(planar_rgb_pack_kernel, dim3((unsigned) ((w + 255) / 256), (unsigned) hh), dim3(256), 0, st, d->plane[0], d->plane[1], d->plane[2],
                                            nullptr, d->plane_pitch[0], d->tmp, 3 * w, w, hh, 0, 0, 8, 16);
                         return ug_hip_pixfmt_convert(UG_PF_RGB, UG_PF_UYVY, d->tmp, dst_dev, w, hh, 0, dst_pitch, 0, 8, 16, stream);

@@ -2023,6 +2023,24 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: output buffer smaller than the JPEG header");
                 return UG_HIP_EINVAL;
         }
+        // the source's pitch and alignment (ug_mi355x.h), here and not in the front ends: the fused kernels read the frame without one, and the
+        // answer must not depend on the path a restart interval or an alignment selects
+        {
+                const int line = in == UG_PF_UYVY ? ug::linesize(UG_PF_UYVY, e->width) : (in == UG_PF_RGBA ? 4 : 3) * e->width;
+                bool ok = true;
+                if (in == UG_PF_I420) {
+                        ok = !src_pitch || src_pitch == e->width;
+                } else if (in == UG_PF_UYVY || in == UG_PF_RGBA) { // 32-bit words: lines (and the frames of a batch) start at multiples of 4
+                        ok = (!src_pitch || (src_pitch >= line && !(src_pitch & 3))) && !(3 & (uintptr_t) src_dev) && (frames == 1 || !(src_stride & 3));
+                } else if (in == UG_PF_RGB) {
+                        ok = !src_pitch || src_pitch >= line;
+                }
+                if (!ok) {
+                        ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: src_pitch must be 0 or at least the line size (I420: 0 or the width); UYVY and RGBA: "
+                                               "src_dev, src_pitch and src_stride multiples of 4");
+                        return UG_HIP_EINVAL;
+                }
+        }
         hipStream_t st = (hipStream_t) stream;
         if (frames > e->batch_cap) { // the work buffers of a frame, once per frame of the batch (grown once; kernels of earlier calls have finished: encode is synchronous)
                 const hipError_t err = alloc_workspace(e, frames);

@@ -618,7 +618,7 @@ int launch_uyvy_jpeg(const void *src, int src_pitch, int width, int height, cons
                 return ug::refuse_size(who);
         }
         if (!src || !div || !out_y || !out_cb || !out_cr || width <= 0 || height <= 0 || frames < 0 || frames > 65535 ||
-            ((uintptr_t) out_y | (uintptr_t) out_cb | (uintptr_t) out_cr) & 15 || (frames > 1 && ((fs.luma | fs.chroma) & 15))) {
+            (src_pitch && src_pitch < ug::linesize(UG_PF_UYVY, width)) || ((uintptr_t) out_y | (uintptr_t) out_cb | (uintptr_t) out_cr) & 15 || (frames > 1 && ((fs.luma | fs.chroma) & 15))) {
                 ug::set_last_error_msg(who);
                 return UG_HIP_EINVAL;
         }
