@@ -172,6 +172,12 @@ __device__ __forceinline__ uint32_t spread16(uint32_t x)
 #ifndef UG_DXT_POW2_FOLD
 #define UG_DXT_POW2_FOLD 1
 #endif
+// DXT5-YCoCg colour stage: with one chroma sample per pixel pair the open comparison da > db is the sign of a linear form of the pixel,
+// taken ONCE per pair from two fma under an error certificate; a wave with an uncertified block evaluates the reference's two squared
+// distances for every pixel (1 = on; 0 = the distances for every pixel; A/B switch).  Only where the pair location (UG_DXT_PAIR_ZONE) is.
+#ifndef UG_DXT_PAIR_LINEAR
+#define UG_DXT_PAIR_LINEAR 1
+#endif
 [[maybe_unused]] constexpr float kIndexBias = 8388608.0f;      // 2^23
 [[maybe_unused]] constexpr uint32_t kIndexBits = 0x4b000000u;  // its bits: lowest set bit 24, so kIndexBits << 8 == 0 (mod 2^32) -- a row offset needs no correction
 // what `fields` accumulations acc = (acc << shift) + (kIndexBits + n) leave in a 32-bit word besides the n (wrap-around arithmetic)
@@ -198,8 +204,21 @@ __device__ __forceinline__ void count_exact_cov()
                 atomicAdd(&g_exact_cov_waves, 1ull);
         }
 }
+// and for the colour stage's linear form (UG_DXT_PAIR_LINEAR): waves that went on to the per-pixel distances.  That side is no rare
+// path -- a few percent of the waves of ordinary video take it, all of them on content built for it -- and atomics on ONE address are served
+// one after the other: 129 600 counting waves per launch cost 1.4 ms beside 0.14 ms of encoding.  So the count is kept in kPairSlots
+// slots, each in a 128-byte line of its own, chosen by workgroup and wave; ug_hip_dxt_encode_stats_ex adds them up.
+constexpr int kPairSlots = 256, kPairSlotStride = 16; // 16 x 8 B = one line
+__device__ unsigned long long g_exact_pair_waves[kPairSlots * kPairSlotStride];
+__device__ __forceinline__ void count_exact_pair()
+{
+        if ((int) threadIdx.x == __builtin_amdgcn_readfirstlane((int) threadIdx.x)) {
+                const uint32_t slot = ((blockIdx.x + 17u * blockIdx.y + 101u * blockIdx.z) * 4u + threadIdx.y) & (kPairSlots - 1); // block = 64 lanes x up to 4 waves
+                atomicAdd(&g_exact_pair_waves[slot * kPairSlotStride], 1ull);
+        }
+}
 struct IndexTables {
-        float *alpha;    // [8][64] floats: thresholds in DESCENDING order, row 7 = -inf
+        float *alpha;   // [8][64] floats: thresholds in DESCENDING order, row 7 = -inf
         float4 *colour;   // DXT5-YCoCg: [3][64] (A.x, A.y, B.x, B.y) of the palette pair whose bisector crosses zone k; DXT1: [6][64], rows 2k / 2k + 1 = A / B (xyz)
 };
 
@@ -983,6 +1002,34 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 // around the borders (and RN's tie on them), which is the case of the paragraph above.  3/2 and -1/4 fold into ka, kb, kc.
                 // These fma only locate; no result of theirs is an operation of the reference.  kIndexBits << 10 (rows of 64 float4)
                 // is 0 mod 2^32, and the zone word collects kIndexBits as a known sum, subtracted once.
+                //
+                // One linear form per chroma pair (PAIRS, UG_DXT_PAIR_ZONE, UG_DXT_PAIR_LINEAR).  The open comparison keeps one bit, da > db,
+                // and in real arithmetic da - db = |p - A|^2 - |p - B|^2 is linear in the pixel p = (Co, Cg).  Half of it is
+                //   H(p) = (B - A) . (p - (A + B) / 2) = n . p + c,   n = B - A,   c = ((A - B) . (A + B)) / 2,
+                // and the rows of the table hold (m.x, m.y, c) of each zone's palette pair instead of (A, B): m = A - B = -n with one rounding
+                // per component, c = fma(m.x, s.x, m.y * s.y) / 2 with s = A + B, about the origin of the colour space (no block-local
+                // origin: the coordinates are small, see below, and a local one costs two subtractions per pair).  The pair gets
+                //   L = fma(-Co, m.x, fma(-Cg, m.y, c))   on its EVEN pixel,   bit = L > 0   for both pixels,
+                // wherever |L| exceeds the sum of what separates L from half the reference's da - db of either pixel.  With u = 2^-24, d =
+                // |B - A| <= 0.334 sqrt(vv) (a third of the segment; c2 / c3 are off their ideal places by < 2e-7 against sqrt(vv) >= 3.1e-3),
+                // palette coordinates in [0, 1] and |Co|, |Cg| < 1.5 (the YUV front ends: Co = 128 / 255 +- 0.98, Cg = 128 / 255 +- 0.68):
+                //   rows and fma   n rounded: u d |p - (A + B) / 2| <= 2.5 u d (both lie in the box, whose diagonal is < 2.5);  s rounded
+                //                  at magnitudes <= 2, the product and the sum of c at <= |mx| + |my| each: u (2 |mx| + 3 |my|) <= 3.7 u d;
+                //                  the inner fma at <= 1.5 |my| + |mx| + |my|: <= 2.7 u d;  the outer one at |L| <= 2.5 d.  In all
+                //                  11.4 u d < 2.3e-7 sqrt(vv).
+                //   the pair       the odd pixel is within 5e-7 of the even one in Co and in Cg (above): |n . dp| <= sqrt(2) 5e-7 d
+                //                  < 2.4e-7 sqrt(vv).
+                //   the reference  each of da, db is off by < 2^-22 dmax (the fast form's own argument, above), half their difference by
+                //                  < 2^-22 dmax.
+                // So |L - (da - db) / 2| < 4.7e-7 sqrt(vv) + 2^-22 dmax for either pixel, and a block is certified where the least |L| of
+                // its eight pairs exceeds
+                //   eps = 1e-6 sqrt(vv) + 2^-21 dmax,
+                // a factor > 2 over the analysis (tests/test_dxt_pair_linear_bound.py restates the stage in strict fp32 and finds the fp32 L
+                // within 0.05 eps of the one formed in double).  A certified L is not 0 and has the sign of da - db for both pixels, so da >
+                // db is L > 0.  Flat blocks are certified as they are: their word is replaced below.  A wave that holds an uncertified block
+                // (a pixel next to a bisector: smooth gradients put some there) writes the rows (A, B) over the linear ones -- the table does
+                // not grow -- and evaluates the reference's two distances for every pixel of all its blocks, in the zones already found:
+                // the parent's stage, operands and order.  These fma only locate; no result of theirs is an operation of the reference.
                 const float vx = cx[1] - cx[0], vy = cy[1] - cy[0];
                 const float vv = vx * vx + vy * vy;
                 const float e0 = fmaxf(fmaxf(mxCo, cx[0]), cx[1]) - fminf(fminf(mnCo, cx[0]), cx[1]);
@@ -993,9 +1040,23 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 const bool flat = (mnCo == mxCo) & (mnCg == mxCg);
                 if (__builtin_expect(__all(((vv >= 1e-5f) & (vv * 256.0f > dmax)) | flat), 1)) {
                         float4 *const tc = tab.colour;
-                        tc[0 * 64] = make_float4(cx[0], cy[0], cx[2], cy[2]); // zone 0: d0 > d2
-                        tc[1 * 64] = make_float4(cx[2], cy[2], cx[3], cy[3]); // zone 1: d2 > d3
-                        tc[2 * 64] = make_float4(cx[1], cy[1], cx[3], cy[3]); // zone 2: d1 > d3
+                        constexpr bool kLinear = PAIRS && UG_DXT_PAIR_ZONE && UG_DXT_PAIR_LINEAR;
+                        auto write_rows = [&](float ax, float ay, float bx, float by, float cx2, float cy2, float cx3, float cy3) {
+                                tc[0 * 64] = make_float4(ax, ay, cx2, cy2);   // zone 0: d0 > d2
+                                tc[1 * 64] = make_float4(cx2, cy2, cx3, cy3); // zone 1: d2 > d3
+                                tc[2 * 64] = make_float4(bx, by, cx3, cy3);   // zone 2: d1 > d3
+                        };
+                        if constexpr (kLinear) {
+                                auto linear_row = [&](int a, int b) { // (-n.x, -n.y, c) of H = half of |p - A|^2 - |p - B|^2, A = palette a, B = palette b
+                                        const float mx = cx[a] - cx[b], my = cy[a] - cy[b], sx = cx[a] + cx[b], sy = cy[a] + cy[b];
+                                        return make_float4(mx, my, 0.5f * __builtin_fmaf(mx, sx, my * sy), 0.0f);
+                                };
+                                tc[0 * 64] = linear_row(0, 2);
+                                tc[1 * 64] = linear_row(2, 3);
+                                tc[2 * 64] = linear_row(1, 3);
+                        } else {
+                                write_rows(cx[0], cy[0], cx[1], cy[1], cx[2], cy[2], cx[3], cy[3]);
+                        }
 #if UG_DXT_BITS_INDEX
                         const float inv = 1.5f * __builtin_amdgcn_rcpf(vv);
                         const float ka = vx * inv, kb = vy * inv;
@@ -1013,6 +1074,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         static_assert(kC % kP == 0, "a group holds whole pairs");
                         float4 e[2][kC / kP];
                         uint32_t kk[2][kC / kP];
+                        [[maybe_unused]] float mag[kC / kP], least = __builtin_inff(); // kLinear: |L| of the group's pairs, the block's least
                         auto fetch = [&](int grp, int slot) {
 #pragma unroll
                                 for (int j = kC - kP; j >= 0; j -= kP) {
@@ -1039,12 +1101,25 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                 for (int j = kC - 1; j >= 0; j--) {
                                         const int i = kC * grp + j;
                                         const float4 q = e[slot][j / kP];
-                                        const float ax = Co[i] - q.x, ay = Cg[i] - q.y, bx = Co[i] - q.z, by = Cg[i] - q.w;
-                                        const float da = ax * ax + ay * ay, db = bx * bx + by * by; // glsl:231-235, same operation order
-                                        if (j % kP == 0) { // one field of 2 * kP bits per location
-                                                zones = (zones << (2 * kP)) + kk[slot][j / kP];
+                                        if constexpr (kLinear) { // one bit per PAIR: open collects eight
+                                                if (j % kP == 0) {
+                                                        const float L = __builtin_fmaf(-Co[i], q.x, __builtin_fmaf(-Cg[i], q.y, q.z)); // negations ride as operand modifiers
+                                                        zones = (zones << (2 * kP)) + kk[slot][j / kP];
+                                                        open = shift_in(open, LANEMASK(L > 0.0f));
+                                                        mag[j / kP] = fabsf(L);
+                                                }
+                                        } else {
+                                                const float ax = Co[i] - q.x, ay = Cg[i] - q.y, bx = Co[i] - q.z, by = Cg[i] - q.w;
+                                                const float da = ax * ax + ay * ay, db = bx * bx + by * by; // glsl:231-235, same operation order
+                                                if (j % kP == 0) { // one field of 2 * kP bits per location
+                                                        zones = (zones << (2 * kP)) + kk[slot][j / kP];
+                                                }
+                                                open = shift_in(open, LANEMASK(da > db));
                                         }
-                                        open = shift_in(open, LANEMASK(da > db));
+                                }
+                                if constexpr (kLinear) { // v_min3_f32 with abs modifiers: one per group
+                                        static_assert(kC / kP == 2, "two pairs per group");
+                                        least = fminf(fminf(least, mag[0]), mag[1]);
                                 }
                                 __builtin_amdgcn_sched_barrier(0);
                         }
@@ -1054,11 +1129,44 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         if (kP == 2) { // pair j's zone sits in bits 4j, 4j + 1 = the field of pixel 2j: copy it to pixel 2j + 1's
                                 zones |= zones << 2;
                         }
-                        const uint32_t c = spread16(open), k0 = zones & 0x55555555u, k1 = (zones >> 1) & 0x55555555u;
+                        uint32_t c;
+                        if constexpr (kLinear) {
+                                const float eps = __builtin_fmaf(dmax, 4.76837158203125e-07f, 1e-6f * __builtin_amdgcn_sqrtf(vv)); // 2^-21 dmax + 1e-6 sqrt(vv)
+                                const lanemask_t certain = LANEMASK(least > eps) | LANEMASK(flat);
+                                if (__builtin_expect(certain == LANEMASK(true), 1)) { // __all, on the two comparisons' own lane masks
+                                        // pair j's bit from bit j to bit 4j = the field of pixel 2j, then to pixel 2j + 1's as well
+                                        c = (open | (open << 12)) & 0x000f000fu;
+                                        c = (c | (c << 6)) & 0x03030303u;
+                                        c = (c | (c << 3)) & 0x11111111u;
+                                        c |= c << 2;
+                                } else {
+                                        // The empty asm keeps this a real branch (see the alpha stage's fallback).
+                                        asm volatile("; per-pixel distances" ::: "memory");
+                                        count_exact_pair();
+                                        write_rows(cx[0], cy[0], cx[1], cy[1], cx[2], cy[2], cx[3], cy[3]);
+                                        open = 0;
+#pragma unroll
+                                        for (int i = 15; i >= 0; i--) { // the pixel's zone sits in bits 2 i, 2 i + 1; a row is 64 float4
+                                                const float4 q = *(const float4 *) ((const char *) tc + (((zones >> (2 * i)) & 3u) << 10));
+                                                const float ax = Co[i] - q.x, ay = Cg[i] - q.y, bx = Co[i] - q.z, by = Cg[i] - q.w;
+                                                const float da = ax * ax + ay * ay, db = bx * bx + by * by; // glsl:231-235, same operation order
+                                                open = shift_in(open, LANEMASK(da > db));
+                                        }
+                                        c = spread16(open);
+                                }
+                        } else {
+                                c = spread16(open);
+                        }
+                        const uint32_t k0 = zones & 0x55555555u, k1 = (zones >> 1) & 0x55555555u;
                         w_cidx = ((k0 & c) | k1) | ((k0 | c) << 1);
                         if (__any(flat)) {
                                 asm volatile("; flat blocks" ::: "memory");
-                                const float4 p02 = tc[0 * 64], p13 = tc[2 * 64]; // the palette, back from the table (not kept in registers)
+                                float4 p02, p13; // the palette, back from the table (not kept in registers) where the table holds it
+                                if constexpr (kLinear) {
+                                        p02 = make_float4(cx[0], cy[0], cx[2], cy[2]); p13 = make_float4(cx[1], cy[1], cx[3], cy[3]);
+                                } else {
+                                        p02 = tc[0 * 64]; p13 = tc[2 * 64];
+                                }
                                 const float px[4] = { p02.x, p13.x, p02.z, p13.z }, py[4] = { p02.y, p13.y, p02.w, p13.w };
                                 float d[4];
 #pragma unroll
@@ -1644,19 +1752,25 @@ extern "C" int ug_hip_dxt_encode_stats(unsigned long long full_form_waves[2], in
                 const unsigned long long zero[2] = { 0, 0 };
                 UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_full_form_waves), zero, sizeof zero));
                 UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_cov_waves), zero, sizeof zero[0]));
+                static const unsigned long long no_pairs[kPairSlots * kPairSlotStride] = {};
+                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_pair_waves), no_pairs, sizeof no_pairs));
         }
         return UG_HIP_SUCCESS;
 }
 
-// The same with the diagonal stage's counter: counts[0 .. n - 1] of { colour full form, alpha full form, exact covariance sum }
+// The same with the counters of the certified stages: counts[0 .. n - 1] of { colour full form, alpha full form, exact covariance sum,
+// per-pixel distances after the colour stage's linear form }
 extern "C" int ug_hip_dxt_encode_stats_ex(unsigned long long *counts, int n, int reset)
 {
-        if (n < 0 || n > 3 || (n > 0 && !counts)) return UG_HIP_EINVAL;
-        unsigned long long all[3] = { 0, 0, 0 };
+        if (n < 0 || n > 4 || (n > 0 && !counts)) return UG_HIP_EINVAL;
+        unsigned long long all[4] = { 0, 0, 0, 0 };
         UG_HIP_TRY(hipDeviceSynchronize());
         if (n > 0) {
                 UG_HIP_TRY(hipMemcpyFromSymbol(all, HIP_SYMBOL(g_full_form_waves), 2 * sizeof all[0]));
                 UG_HIP_TRY(hipMemcpyFromSymbol(all + 2, HIP_SYMBOL(g_exact_cov_waves), sizeof all[0]));
+                static unsigned long long pairs[kPairSlots * kPairSlotStride]; // (this function synchronises the device: diagnostics, one caller at a time)
+                UG_HIP_TRY(hipMemcpyFromSymbol(pairs, HIP_SYMBOL(g_exact_pair_waves), sizeof pairs));
+                for (int i = 0; i < kPairSlots; i++) all[3] += pairs[i * kPairSlotStride];
                 for (int i = 0; i < n; i++) counts[i] = all[i];
         }
         return reset ? ug_hip_dxt_encode_stats(nullptr, 1) : UG_HIP_SUCCESS;
