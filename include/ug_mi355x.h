@@ -475,6 +475,77 @@ int ug_hip_gamma_lut(double gamma, int in_bits, int out_bits, void *table_host);
 /* matrix2's named matrices (matrix2.c:69-73,113): "y601_to_y709".  Unknown name: UG_HIP_EINVAL. */
 int ug_hip_matrix2_preset(const char *name, double m[9]);
 
+/* Frame composition: the geometric and compositing postprocessors / capture filters on device frames of `lines` lines of `width` pixels, byte for
+ * byte what the reference's C computes where that stays inside its buffers (the rest: "Deviations" below):
+ *   UG_CMP_CROP           src/vo_postprocess/crop.c:159-182: dst line y = out_line_bytes bytes of src line yoff + y from byte xoff_bytes; out_lines
+ *                         lines.  Works in bytes: every packed format.  ug_hip_crop_geometry gives the four numbers as the reference derives them.
+ *   UG_CMP_BORDER         src/vo_postprocess/border.c:158-208: src copied, the top and bottom border_h lines and border_w pixels at either side filled
+ *                         with `fill` (UG_PF_RGB: its first 3 bytes; UG_PF_RGBA: all 4; UG_PF_UYVY: the word U Y V Y, rows filled over the whole line
+ *                         size, sides ceil(border_w / 2) pairs from each end).  ug_hip_border_pattern gives `fill` for a colour.
+ *   UG_CMP_LOGO           src/capture_filter/logo.c:182-230: the R,G,B,A overlay `logo` (device, logo_w x logo_h x 4 bytes) blended IN PLACE into dst
+ *                         (src NULL or == dst) at pixel (rect_x, rect_y): per pixel the reference's decoder to 8-bit RGB, c = (c * (255 - a) + l * a) /
+ *                         255, its coder back.  UG_PF_UYVY (Q14 both ways, the pair's chroma from both blended pixels; an odd logo_w re-encodes the
+ *                         whole last pair, its second pixel unblended), UG_PF_RGB, UG_PF_RGBA (alpha comes back 0xFF), UG_PF_RG48 (the high bytes; the
+ *                         low bytes come back 0).  The frame under the logo changes even where alpha is 0.  rect_x or rect_y < 0: success, nothing done
+ *                         (logo.c:195-196).  ug_hip_logo_geometry gives the rectangle, the reference's rounding slip included.
+ *   UG_CMP_INTERLACE      src/vo_postprocess/interlace.c:172-181: dst line i = line i of src (the first frame of the pair) for even i, of src2 for odd i.
+ *   UG_CMP_INTERLACED_3D  src/vo_postprocess/3d-interlaced.c:152-169: dst line x = per BYTE (a + b + 1) >> 1 of lines (x / 2) * 2 and (x / 2) * 2 + 1 of
+ *                         eye x % 2 (src = tile 0, src2 = tile 1), whatever the format, as pavgb does (wrong for v210's 10-bit fields, reproduced).
+ *   UG_CMP_SPLIT          src/utils/vf_split.cpp:79-108: tile (tx, ty) of grid_x x grid_y at dst + (ty * grid_x + tx) * tile_stride, its lines tile_pitch
+ *                         apart (0: vc_get_linesize(tile width)), each tile_width * get_bpp bytes from byte tx * that of the source line; tile_stride 0 =
+ *                         tile_pitch * tile lines; dst_pitch is not used.  The grid must divide width and lines (UG_HIP_EINVAL); v210 / DVS10 / R12L tiles
+ *                         must be whole pixel blocks (UG_HIP_EUNSUPP).
+ * Deviations and refusals, where the reference leaves its buffers: LOGO blends every logo pixel over its own decoded frame pixel (the reference's RGB
+ * segment is (logo_w + 1) / bb * bb pixels wide, logo.c:198-222: narrower than the logo for logo_w % 4 in {1, 2} on UYVY / RGBA, % 3 == 1 on RGB, % 6 not
+ * in {0, 5} on RG48, where its blend runs into the next line and past the allocation); a LOGO rectangle that leaves the frame is refused (the
+ * reference's rounding toward zero draws a logo up to bb - 1 pixels wider than the frame across the line ends); INTERLACED_3D writes lines at dst_pitch,
+ * linesize bytes each (the reference advances 16 bytes per step across lines, :157-168) and refuses an odd `lines`; BORDER refuses border_w > width and
+ * 2 * border_h > lines (border.c:158,181-184,203-206); CROP copies out_line_bytes bytes (the reference: req_pitch, crop.c:176-178) and refuses
+ * xoff_bytes + out_line_bytes beyond the source's line size.
+ * Pitches 0 = the line size (CROP's dst: out_line_bytes), otherwise at least that; the ops work in bytes: any pointer, pitch and stride (LOGO on
+ * UG_PF_RG48: multiples of 2); lines 1..65536, at most INT_MAX bytes per frame, frames 1..65535 (grid.z), frame i at src (src2) + i * src_frame_stride ->
+ * dst + i * dst_frame_stride, the one overlay on every frame.  Sources and destination must not overlap (LOGO: the overlay and the frame).  An op /
+ * format pair without a kernel: UG_HIP_EUNSUPP; anything else: UG_HIP_EINVAL; both before any device call.  Units of 16 bytes at multiples of 16 take
+ * the dwordx4 path; bytes of a destination line past the written size keep their content. */
+#define UG_CMP_CROP          0
+#define UG_CMP_BORDER        1
+#define UG_CMP_LOGO          2
+#define UG_CMP_INTERLACE     3
+#define UG_CMP_INTERLACED_3D 4
+#define UG_CMP_SPLIT         5
+struct ug_compose_desc {
+        const void *src;            /* device (LOGO: NULL or dst) */
+        const void *src2;           /* device: INTERLACE's second frame, INTERLACED_3D's second eye; same pitch and stride as src */
+        void       *dst;            /* device */
+        int         op;             /* UG_CMP_* */
+        ug_pixfmt_t format;
+        int         width, lines;   /* the source frame (LOGO: the frame), pixels and lines */
+        size_t      src_pitch, dst_pitch;
+        int         frames;
+        size_t      src_frame_stride, dst_frame_stride;
+        int         xoff_bytes, yoff, out_line_bytes, out_lines;  /* CROP */
+        int         border_w, border_h;                           /* BORDER: pixels, lines */
+        unsigned char fill[4];                                    /* BORDER */
+        const void *logo;                                         /* LOGO: device, R,G,B,A, logo_w * 4 bytes per line */
+        int         logo_w, logo_h, rect_x, rect_y;               /* LOGO: pixels */
+        int         grid_x, grid_y;                               /* SPLIT */
+        size_t      tile_pitch, tile_stride;                      /* SPLIT: bytes */
+};
+int ug_hip_compose(const struct ug_compose_desc *d, ug_hip_stream_t stream);
+int ug_hip_compose_supported(int op, ug_pixfmt_t format); /* 1 / 0 */
+/* crop.c:141-148,170-173 (host): the output size cut down to whole pixel blocks ((int) (w * get_bpp) / block bytes * block bytes, get_bpp a double: 8 / 3
+ * for v210, 4.5 for R12L; want 0 = the frame's), the offsets moved back so that the rectangle stays in the frame, x rounded down to whole blocks in
+ * bytes.  *out_w can come out 0 (a UYVY crop one pixel wide).  Frame sizes 1..65536, the others 0..65536, else UG_HIP_EINVAL. */
+int ug_hip_crop_geometry(ug_pixfmt_t format, int in_w, int in_h, int want_w, int want_h, int xoff, int yoff, int *out_w, int *out_h, int *xoff_bytes,
+                         int *yoff_out);
+/* logo.c:182-193 (host): rect_x = x, or frame_w - logo_w where x < 0 or x + logo_w > frame_w, then rect_x / bb * bb with bb = get_pf_block_bytes -- a
+ * pixel position rounded by the block's BYTE count, C's division toward zero; rect_y the same without the rounding.  A negative result: the frame is
+ * left as it is. */
+int ug_hip_logo_geometry(ug_pixfmt_t format, int frame_w, int frame_h, int logo_w, int logo_h, int x, int y, int *rect_x, int *rect_y);
+/* BORDER's `fill` for a colour R,G,B,A (host): UG_PF_RGB / UG_PF_RGBA the four bytes, UG_PF_UYVY what vc_copylineRGBAtoUYVY makes of two copies of
+ * the colour (border.c:161-166). */
+int ug_hip_border_pattern(ug_pixfmt_t format, const unsigned char rgba[4], unsigned char out[4]);
+
 /* packed -> planar (to_planar.h:53-74) */
 int ug_hip_uyvy_to_i420(const void *src_dev, int src_pitch, void *y, int y_pitch, void *u, int u_pitch,
                         void *v, int v_pitch, int width, int height, ug_hip_stream_t stream); /* uyvy_to_i420, to_planar.c:343 */

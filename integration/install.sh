@@ -24,6 +24,7 @@ cp "$M/ldgm_gpu_mi355x.cpp"                  "$UG/src/rtp/ldgm_gpu_mi355x.cpp"
 cp "$M/mi355x_receiver.h"                    "$UG/src/rtp/"
 cp "$M/vo_pp_scale_mi355x.c"                "$UG/src/vo_postprocess/scale_mi355x.c"
 cp "$M/vo_pp_deinterlace_mi355x.c"          "$UG/src/vo_postprocess/deinterlace_mi355x.c"
+cp "$M/vo_pp_compose_mi355x.c"              "$UG/src/vo_postprocess/compose_mi355x.c"
 cp "$M/mi355x_receiver.h" "$M/ug_codec_map.h" "$UG/src/vo_postprocess/"
 cp "$M/capture_filter_pixel_mi355x.c"       "$UG/src/capture_filter/pixel_mi355x.c"
 cp "$M/mi355x_receiver.h" "$M/ug_codec_map.h" "$UG/src/capture_filter/"
@@ -32,4 +33,4 @@ if grep -q "found_ug_mi355x" "$UG/configure.ac"; then
 else
         patch -p1 -d "$UG" < "$HERE/ultragrid_mi355x.patch"
 fi
-echo "installed into $UG: 6 modules, the scale and de-interlacing postprocessors, the colour / mirror filters, the lavc hook and the ldgm_gpu library; configure with --with-ug-mi355x=<prefix>"
+echo "installed into $UG: 6 modules, the scale and de-interlacing postprocessors, the colour / mirror filters, the composition filters, the lavc hook and the ldgm_gpu library; configure with --with-ug-mi355x=<prefix>"

@@ -13,6 +13,7 @@ insertions into configure.ac, nothing removed --
      configure decided scale=no (the GL module is not built),
   7. the de-interlacers (src/vo_postprocess/deinterlace_mi355x.o) in a block of their own behind it,
   8. the colour / mirror capture filters and postprocessors (src/capture_filter/pixel_mi355x.o) in a block of their own behind that,
+  9. the geometric / compositing postprocessors and capture filters (src/vo_postprocess/compose_mi355x.o) in a block of their own behind that,
   5. the ldgm_gpu library (src/rtp/ldgm_gpu_mi355x.o) where LDGM is on and the CUDA ldgm_gpu is not built: in front of the LDGM GPU
      section's ENSURE_FEATURE_PRESENT, so that --enable-ldgm-gpu without CUDA succeeds when libug_mi355x is found (the detection of 1.
      runs earlier in configure.ac than the LDGM section).
@@ -124,6 +125,15 @@ then
 fi
 '''
 
+COMPOSE = '''
+# frame composition on the MI355X, beside the CPU modules (crop_mi355x, border_mi355x, interlace_mi355x, interlaced_3d_mi355x, split_mi355x, logo_mi355x;
+# postprocessors and capture filters: one object registers both classes)
+if test "${found_ug_mi355x?}" = yes
+then
+        add_module vo_pp_compose_mi355x "src/vo_postprocess/compose_mi355x.o" "$UG_MI355X_LIB"
+fi
+'''
+
 SUMMARY = 'add_column "MI355X DXT/JPEG" "${ug_mi355x?}"\n'
 
 
@@ -157,7 +167,7 @@ def main():
     # 3. behind the CUDA DXT section
     new = insert_after(new, "ENSURE_FEATURE_PRESENT([$cuda_dxt_req], [$cuda_dxt], [CUDA DXT not found])", MODULES)
     # 6. the `scale` stand-in, behind the Scale section (where scale is decided)
-    new = insert_after(new, "ENSURE_FEATURE_PRESENT([$scale_req], [$scale], [Scale not found])", SCALE + DEINT + PIXEL)
+    new = insert_after(new, "ENSURE_FEATURE_PRESENT([$scale_req], [$scale], [Scale not found])", SCALE + DEINT + PIXEL + COMPOSE)
     # 5. the MI355X ldgm_gpu, in front of the LDGM GPU section's check
     new = insert_before(new, "ENSURE_FEATURE_PRESENT([$ldgm_gpu_req], [$ldgm_gpu], [LDGM accelerated GPU cannot be enabled (CUDA not found?)])", LDGM)
     # 4. summary table, behind "Lavc ..." keeps the list alphabetical enough: in front of OpenAPV

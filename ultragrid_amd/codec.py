@@ -187,6 +187,82 @@ def pixel_filter(op: int, fmt: int, src: torch.Tensor, w: int, lines: int, matri
     return dst
 
 
+def crop_geometry(fmt: int, in_w: int, in_h: int, want_w: int = 0, want_h: int = 0, xoff: int = 0, yoff: int = 0):
+    """crop.c's geometry (ug_hip_crop_geometry) -> (out_w, out_h, xoff_bytes, yoff)"""
+    r = [C.c_int(0) for _ in range(4)]
+    L.check(L.load().ug_hip_crop_geometry(fmt, in_w, in_h, want_w, want_h, xoff, yoff, *[C.byref(v) for v in r]), "ug_hip_crop_geometry")
+    return tuple(v.value for v in r)
+
+
+def logo_geometry(fmt: int, frame_w: int, frame_h: int, logo_w: int, logo_h: int, x: int = -1, y: int = -1):
+    """logo.c's rectangle (ug_hip_logo_geometry) -> (rect_x, rect_y); a negative one leaves the frame as it is"""
+    rx, ry = C.c_int(0), C.c_int(0)
+    L.check(L.load().ug_hip_logo_geometry(fmt, frame_w, frame_h, logo_w, logo_h, x, y, C.byref(rx), C.byref(ry)), "ug_hip_logo_geometry")
+    return rx.value, ry.value
+
+
+def border_pattern(fmt: int, rgba) -> bytes:
+    """border.c's fill word for a colour (ug_hip_border_pattern)"""
+    a, out = (C.c_ubyte * 4)(*rgba), (C.c_ubyte * 4)()
+    L.check(L.load().ug_hip_border_pattern(fmt, a, out), "ug_hip_border_pattern")
+    return bytes(out)
+
+
+def compose(op: int, fmt: int, src: torch.Tensor, w: int, lines: int, src2: torch.Tensor | None = None, crop=None, border=None, logo=None, grid=None,
+            frames: int = 1, src_pitch: int = 0, dst_pitch: int = 0, dst: torch.Tensor | None = None) -> torch.Tensor:
+    """The reference's geometric / compositing filters on the device (ug_hip_compose).  L.CMP_CROP: crop = (want_w, want_h, xoff, yoff) as the
+    module's options; L.CMP_BORDER: border = (border_w, border_h, (r, g, b, a)); L.CMP_LOGO: logo = (overlay R,G,B,A device tensor, logo_w, logo_h,
+    x, y), blended into `src` in place, which is returned; L.CMP_INTERLACE / L.CMP_INTERLACED_3D: `src2` = the second frame / eye; L.CMP_SPLIT:
+    grid = (x, y), the tiles back to back.  `frames` pictures of `lines` lines `src_pitch` (0: the line size) apart, back to back, in and out."""
+    src = _u8(src)
+    ls = linesize(fmt, w)
+    sp = src_pitch or ls
+    d = L.ComposeDesc(src=src.data_ptr(), op=op, format=fmt, width=w, lines=lines, src_pitch=sp, frames=frames, src_frame_stride=sp * lines)
+    out_line, out_lines = ls, lines
+    if src.numel() < frames * sp * lines:
+        raise ValueError("tensor smaller than the frames it should hold")
+    if op == L.CMP_CROP:
+        ow, oh, d.xoff_bytes, d.yoff = crop_geometry(fmt, w, lines, *crop)
+        if ow < 1:
+            raise ValueError("the crop is narrower than one pixel block")
+        d.out_line_bytes, d.out_lines = min(linesize(fmt, ow), ls - d.xoff_bytes), oh
+        out_line, out_lines = d.out_line_bytes, oh
+    elif op == L.CMP_BORDER:
+        d.border_w, d.border_h = border[0], border[1]
+        d.fill = (C.c_ubyte * 4)(*border_pattern(fmt, border[2]))
+    elif op == L.CMP_LOGO:
+        overlay, d.logo_w, d.logo_h = _u8(logo[0]), logo[1], logo[2]
+        if overlay.numel() < 4 * d.logo_w * d.logo_h:
+            raise ValueError("overlay smaller than logo_w * logo_h * 4 bytes")
+        d.logo = overlay.data_ptr()
+        d.rect_x, d.rect_y = logo_geometry(fmt, w, lines, d.logo_w, d.logo_h, *logo[3:5])
+        d.src, d.dst, d.dst_pitch, d.dst_frame_stride = None, src.data_ptr(), sp, sp * lines
+        L.check(L.load().ug_hip_compose(C.byref(d), _stream()), "ug_hip_compose")
+        return src
+    elif op in (L.CMP_INTERLACE, L.CMP_INTERLACED_3D):
+        src2 = _u8(src2)
+        if src2.numel() < frames * sp * lines:
+            raise ValueError("second tensor smaller than the frames it should hold")
+        d.src2 = src2.data_ptr()
+    elif op == L.CMP_SPLIT:
+        d.grid_x, d.grid_y = grid
+        if d.grid_x < 1 or d.grid_y < 1 or w % d.grid_x or lines % d.grid_y:
+            raise ValueError("the grid must divide the frame")
+        out_line, out_lines = linesize(fmt, w // d.grid_x), lines * d.grid_x  # every tile line, tile after tile
+        dst_pitch = 0
+    dp = dst_pitch or out_line
+    if dst is None:
+        dst = torch.zeros(frames * dp * out_lines, dtype=torch.uint8, device=src.device)
+    dst = _u8(dst)
+    if dst.numel() < frames * dp * out_lines:
+        raise ValueError("destination smaller than the frames it should hold")
+    d.dst, d.dst_frame_stride = dst.data_ptr(), dp * out_lines
+    if op != L.CMP_SPLIT:
+        d.dst_pitch = dp
+    L.check(L.load().ug_hip_compose(C.byref(d), _stream()), "ug_hip_compose")
+    return dst
+
+
 def uyvy_to_i420(src: torch.Tensor, w: int, h: int):
     src = _u8(src)
     cw, ch = (w + 1) // 2, (h + 1) // 2

@@ -11,6 +11,7 @@
 //   * fast (hot formats, aligned geometry): one lane per 16..32 input bytes, 128-bit loads,
 //     wave accesses contiguous -- these are pure HBM-bandwidth kernels.
 #include "ug_common.h"
+#include "rgb_yuv_device.h"
 
 namespace ug {
 // uyvy_gl.hip: RGB / RGBA -> UG_PF_UYVY_GL (rgba_to_yuv422.glsl)
@@ -19,17 +20,15 @@ int uyvy_gl_convert(ug_pixfmt_t in, const void *src, void *dst, int width, int h
 
 namespace {
 
-// Q14 coefficients, BT.709 limited range (the default, color_space.c:149-191).  Values are the
-// compile-time table of the reference, reproduced by oracle/pixfmt_oracle.c:oracle_color_coeffs
-// and pinned against get_color_coeffs() in tests/test_oracle_pixfmt.py.
-struct Cfs {
-        int y_r, y_g, y_b, cb_r, cb_g, cb_b, cr_r, cr_g, cr_b, y_scale, r_cr, g_cb, g_cr, b_cb;
-};
-__device__ constexpr Cfs kCfs8  = { 2992, 10063, 1016, -1649, -5547, 7196, 7195, -6536, -659, 19077, 29371, -3494, -8733, 34610 };
-__device__ constexpr Cfs kCfs10 = { 2983, 10034, 1013, -1644, -5531, 7175, 7174, -6517, -657, 19133, 29457, -3504, -8758, 34712 };
-constexpr int kBase = 14; // COMP_BASE, color_space.h:70-71
+// Q14 coefficients and the per-pixel / per-pair conversions: rgb_yuv_device.h (shared with compose.hip)
+using ug::Cfs;
+using ug::kBase;
+using ug::kCfs8;
+using ug::kCfs10;
+using ug::clampi;
+using ug::opaque;
+using ug::yuv_to_rgb8;
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ uint32_t ld32(const uint8_t *p)
 {
         return (uint32_t) p[0] | (uint32_t) p[1] << 8 | (uint32_t) p[2] << 16 | (uint32_t) p[3] << 24;
@@ -82,23 +81,6 @@ struct SwapYUYV { // pixfmt_conv.c:136-198
                 d[0] = b; d[1] = a; d[2] = e; d[3] = c;
         }
 };
-// hipcc (ROCm 7.2) fuses "clamp(x >> 14, 0, 255) | clamp(y >> 14, 0, 255) << 8" into gfx950's
-// v_ashr_pk_u8_i32 and then ORs further bytes into the result assuming its upper 16 bits are zero;
-// on MI355X the instruction leaves the destination's upper half unchanged, so stale bytes leak into
-// the packed word (caught by tests/test_gpu_pixfmt.py).  Making the clamped value opaque keeps the
-// clamp (v_med3_i32) and the byte packing as separate, correct instructions at zero run-time cost.
-__device__ __forceinline__ int opaque(int v)
-{
-        asm volatile("" : "+v"(v));
-        return v;
-}
-__device__ __forceinline__ void yuv_to_rgb8(int y, int u, int v, uint8_t *o)
-{
-        // copylineYUVtoRGB, pixfmt_conv.c:1065-1094: clamp [0,255]
-        o[0] = opaque(clampi((y + v * kCfs8.r_cr) >> kBase, 0, 255));
-        o[1] = opaque(clampi((y + u * kCfs8.g_cb + v * kCfs8.g_cr) >> kBase, 0, 255));
-        o[2] = opaque(clampi((y + u * kCfs8.b_cb) >> kBase, 0, 255));
-}
 struct UYVYtoRGB { // pixfmt_conv.c:1102-1108
         static __device__ __host__ int units(int dl) { return dl / 6; }
         static __device__ void run(uint8_t *d, const uint8_t *s, int k, const Args &)
@@ -134,6 +116,7 @@ struct ToUYVY { // vc_copylineToUYVY, pixfmt_conv.c:1008-1053
         static __device__ void run(uint8_t *d, const uint8_t *s, int k, const Args &)
         {
                 s += 2 * PS * k; d += 4 * k;
+                // (ug::rgb_pair_to_uyvy states the same on six values; here the second pixel is fetched after the first one's products)
                 int r = s[RO], g = s[GO], b = s[BO];
                 const int y1 = ((r * kCfs8.y_r + g * kCfs8.y_g + b * kCfs8.y_b) >> kBase) + 16;
                 int u = r * kCfs8.cb_r + g * kCfs8.cb_g + b * kCfs8.cb_b;

@@ -144,6 +144,11 @@ SYMBOLS = {
     "ug_hip_pixel_filter_supported": (_i, [_i, _i]),
     "ug_hip_gamma_lut": (_i, [C.c_double, _i, _i, _vp]),
     "ug_hip_matrix2_preset": (_i, [C.c_char_p, C.POINTER(C.c_double)]),
+    "ug_hip_compose": (_i, [_vp, _vp]),
+    "ug_hip_compose_supported": (_i, [_i, _i]),
+    "ug_hip_crop_geometry": (_i, [_i, _i, _i, _i, _i, _i, _i] + [C.POINTER(_i)] * 4),
+    "ug_hip_logo_geometry": (_i, [_i, _i, _i, _i, _i, _i, _i] + [C.POINTER(_i)] * 2),
+    "ug_hip_border_pattern": (_i, [_i, _vp, _vp]),
 }
 
 
@@ -171,6 +176,18 @@ class PixelFilterDesc(C.Structure):
     _fields_ = [("src", _vp), ("dst", _vp), ("op", _i), ("format", _i), ("out_format", _i), ("width", _i), ("lines", _i),
                 ("src_pitch", _sz), ("dst_pitch", _sz), ("frames", _i), ("src_frame_stride", _sz), ("dst_frame_stride", _sz),
                 ("matrix", C.c_double * 9), ("clamp", _i), ("lut_dev", _vp)]
+
+
+CMP_CROP, CMP_BORDER, CMP_LOGO, CMP_INTERLACE, CMP_INTERLACED_3D, CMP_SPLIT = range(6)
+
+
+class ComposeDesc(C.Structure):
+    """struct ug_compose_desc (include/ug_mi355x.h): ug_hip_compose's frames, geometry and the fields of its six ops"""
+    _fields_ = [("src", _vp), ("src2", _vp), ("dst", _vp), ("op", _i), ("format", _i), ("width", _i), ("lines", _i),
+                ("src_pitch", _sz), ("dst_pitch", _sz), ("frames", _i), ("src_frame_stride", _sz), ("dst_frame_stride", _sz),
+                ("xoff_bytes", _i), ("yoff", _i), ("out_line_bytes", _i), ("out_lines", _i), ("border_w", _i), ("border_h", _i),
+                ("fill", C.c_ubyte * 4), ("logo", _vp), ("logo_w", _i), ("logo_h", _i), ("rect_x", _i), ("rect_y", _i),
+                ("grid_x", _i), ("grid_y", _i), ("tile_pitch", _sz), ("tile_stride", _sz)]
 
 
 class UgHipError(RuntimeError):
