@@ -78,19 +78,66 @@ void av_frame_free(AVFrame **f)
         *f = NULL;
 }
 
+/* ---- frame layout switch (tests/lavc_layout.py): which line sizes, base addresses and initial contents av_frame_get_buffer hands out ---- */
+static int g_layout_mode = UG_STUB_LAYOUT_DEFAULT, g_layout_unit = 1, g_layout_fill = 0;
+
+void ug_stub_set_frame_layout(int mode, int unit, int fill)
+{
+        g_layout_mode = mode;
+        g_layout_unit = unit > 0 ? unit : 1;
+        g_layout_fill = fill & 0xff;
+}
+
+static int line_bytes(const struct fmt_info *fi, int plane, int width)
+{
+        /* packed 4:2:2 formats store bytes[0] per PIXEL of an even-rounded line */
+        int w = plane ? (width + (1 << fi->cw) - 1) >> fi->cw : width;
+        if (fi->planes == 1 && fi->cw) w = (width + 1) / 2 * 2;
+        return w * fi->bytes[plane];
+}
+
+int ug_stub_plane_line_bytes(int format, int plane, int width)
+{
+        const struct fmt_info *fi = info((enum AVPixelFormat) format);
+        if (!fi || plane < 0 || plane >= fi->planes) return 0;
+        return line_bytes(fi, plane, width);
+}
+
 int av_frame_get_buffer(AVFrame *f, int align)
 {
         (void) align;
         const struct fmt_info *fi = info((enum AVPixelFormat) f->format);
         if (!fi) return -1;
         for (int i = 0; i < fi->planes; i++) {
-                /* packed 4:2:2 formats store bytes[0] per PIXEL of an even-rounded line */
-                int w = i ? (f->width + (1 << fi->cw) - 1) >> fi->cw : f->width;
-                if (fi->planes == 1 && fi->cw) w = (f->width + 1) / 2 * 2;
+                const int lb = line_bytes(fi, i, f->width);
                 const int h = i ? (f->height + (1 << fi->ch) - 1) >> fi->ch : f->height;
-                f->linesize[i] = (w * fi->bytes[i] + 63) / 64 * 64; /* padded lines, as FFmpeg's allocator makes them */
-                f->stub_buf[i] = calloc((size_t) f->linesize[i] * (h + 1) + 64, 1);
-                f->data[i] = f->stub_buf[i];
+                const int padded = (lb + 63) / 64 * 64; /* padded lines, as FFmpeg's allocator makes them */
+                if (g_layout_mode == UG_STUB_LAYOUT_DEFAULT) {
+                        f->linesize[i] = padded;
+                        f->stub_size[i] = (size_t) f->linesize[i] * (h + 1) + 64;
+                        f->stub_buf[i] = calloc(f->stub_size[i], 1);
+                        f->data[i] = f->stub_buf[i];
+                        continue;
+                }
+                /* every other mode: front guard, the lines and one spare line, back guard, all of them `fill`, at a 256-byte aligned address */
+                int mode = g_layout_mode, front = UG_STUB_GUARD;
+                if (mode == UG_STUB_LAYOUT_LAST_PLANE_OFF) mode = i == fi->planes - 1 ? UG_STUB_LAYOUT_OFFSET : UG_STUB_LAYOUT_DEFAULT;
+                switch (mode) {
+                case UG_STUB_LAYOUT_TIGHT: f->linesize[i] = lb; break;
+                case UG_STUB_LAYOUT_ODD:
+                        f->linesize[i] = lb + g_layout_unit;
+                        if (f->linesize[i] % 16 == 0) f->linesize[i] += g_layout_unit;
+                        break;
+                case UG_STUB_LAYOUT_OFFSET:
+                        f->linesize[i] = padded + 64;
+                        front += g_layout_unit;
+                        break;
+                default: f->linesize[i] = padded; break;
+                }
+                f->stub_size[i] = (size_t) front + (size_t) f->linesize[i] * (h + 1) + UG_STUB_GUARD;
+                if (posix_memalign(&f->stub_buf[i], 256, f->stub_size[i])) return -1;
+                memset(f->stub_buf[i], g_layout_fill, f->stub_size[i]);
+                f->data[i] = (uint8_t *) f->stub_buf[i] + front;
         }
         return 0;
 }
@@ -183,3 +230,12 @@ int ug_stub_plane_rows(int format, int plane, int height)
         if (!fi || plane >= fi->planes) return 0;
         return plane ? (height + (1 << fi->ch) - 1) >> fi->ch : height;
 }
+int ug_stub_plane_span(const AVFrame *f, int plane, void **base, size_t *size)
+{
+        if (!f || plane < 0 || plane >= AV_NUM_DATA_POINTERS || !f->stub_buf[plane]) return -1;
+        *base = f->stub_buf[plane];
+        *size = f->stub_size[plane];
+        return 0;
+}
+int ug_stub_format_count(void) { return (int) N_FMTS; }
+const char *ug_stub_format_name(int idx) { return idx >= 0 && (size_t) idx < N_FMTS ? k_fmts[idx].name : NULL; }

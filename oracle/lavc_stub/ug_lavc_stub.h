@@ -55,6 +55,7 @@ typedef struct AVFrame {
         enum AVColorRange color_range;
         void *opaque;
         void *stub_buf[AV_NUM_DATA_POINTERS];
+        size_t stub_size[AV_NUM_DATA_POINTERS]; /* bytes of stub_buf[i], guards and spare line included */
 } AVFrame;
 typedef struct AVCodecContext AVCodecContext;
 typedef struct AVCodec AVCodec;
@@ -76,6 +77,16 @@ int av_frame_make_writable(AVFrame *f);
 const char *av_get_pix_fmt_name(enum AVPixelFormat f);
 const AVPixFmtDescriptor *av_pix_fmt_desc_get(enum AVPixelFormat f);
 const char *av_color_space_name(enum AVColorSpace s);
+
+/* Layout switch of av_frame_get_buffer, for the tests of line sizes and plane addresses (tests/lavc_layout.py).  DEFAULT: lines rounded up
+ * to 64 bytes, zeroed, planes as allocated.  Every other mode puts UG_STUB_GUARD bytes in front of a plane and behind its spare line and
+ * sets every byte to `fill`: TIGHT: linesize = the line's own bytes; ODD: that + unit, + unit again if a multiple of 16; OFFSET: 64-rounded
+ * + 64 with data[i] `unit` bytes past a 256-byte aligned address; LAST_PLANE_OFF: 64-rounded lines, the last plane as in OFFSET. */
+enum { UG_STUB_LAYOUT_DEFAULT = 0, UG_STUB_LAYOUT_TIGHT, UG_STUB_LAYOUT_ODD, UG_STUB_LAYOUT_OFFSET, UG_STUB_LAYOUT_LAST_PLANE_OFF };
+#define UG_STUB_GUARD 256
+void ug_stub_set_frame_layout(int mode, int unit, int fill);
+int ug_stub_plane_line_bytes(int format, int plane, int width);                    /* bytes of a line before any rounding */
+int ug_stub_plane_span(const AVFrame *f, int plane, void **base, size_t *size);    /* the whole allocation behind data[plane] */
 #ifdef __cplusplus
 }
 #endif

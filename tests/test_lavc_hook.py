@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import lavc_layout as LL
 import test_lavc_conv as T
 
 HOOK = os.path.join(T.HERE, "..", "oracle", "_ref", "libugref_lavc_hook.so")
@@ -33,7 +34,7 @@ def hook_lib():
                                    ("R10k", "yuv420p10le"), ("R12L", "yuv444p12le")])
 def test_reference_to_lavc_runs_on_the_gpu(hip, capfd, monkeypatch, uv, av):
     monkeypatch.setenv("UG_MI355X_VERBOSE", "1")
-    h, r = hook_lib(), T.ref()
+    h, r = LL.ref(hook_lib()), LL.ref()
     for (w, h_) in [(48, 8), (96, 6)]:
         ls = r.vc_get_linesize(w, r.get_codec_from_name(uv.encode()))
         src = np.random.default_rng(w).integers(0, 256, ls * h_ + 64).astype(np.uint8)
@@ -47,6 +48,21 @@ def test_reference_to_lavc_runs_on_the_gpu(hip, capfd, monkeypatch, uv, av):
         h.to_lavc_vid_conv_destroy(C.byref(stp))
         for k, (g, wnt) in enumerate(zip(got, want)):
             assert np.array_equal(g, wnt), (uv, av, w, h_, k)
+        # the same with frames of tight lines and of planes a sample past an aligned address (tests/lavc_layout.py), 0xA5 beforehand: the
+        # hook build has its own copy of the FFmpeg stand-in, so the layout is switched there as well
+        for layout in ("tight", "offset"):
+            want = LL.ref_uv_to_av_laid_out(r, uv, av, [src], w, h_, layout)[1]
+            with LL.laid_out(h, layout, LL.frame_unit(av)):
+                st = h.to_lavc_vid_conv_init(h.get_codec_from_name(uv.encode()), w, h_, h.ug_stub_pixfmt_by_name(av.encode()), 1)
+            assert st
+            fr = h.to_lavc_vid_conv(st, src.ctypes.data)
+            assert fr, "the hook returned no frame"
+            got = [p.copy() for p in LL.frame_planes(h, fr.contents, h_)]
+            stp = C.c_void_p(st)
+            h.to_lavc_vid_conv_destroy(C.byref(stp))
+            for k, (g, wnt) in enumerate(zip(got, want)):
+                assert (g.ls, g.off) == (wnt.ls, wnt.off) and np.array_equal(g.lines(), wnt.lines()), (uv, av, w, h_, layout, k)
+                assert (g.whole[: g.off] == LL.FILL).all() and (g.whole[g.off + (g.rows + 1) * g.ls:] == LL.FILL).all(), (uv, av, w, h_, layout, k)
     assert f"to_lavc {uv} -> {av} on the device" in capfd.readouterr().err
 
 
@@ -55,20 +71,21 @@ def test_reference_to_lavc_runs_on_the_gpu(hip, capfd, monkeypatch, uv, av):
 def test_reference_from_lavc_runs_on_the_gpu(hip, capfd, monkeypatch, uv):
     """from_lavc_cuda_supp_formats lists yuv422p (from_lavc_vid_conv_cuda.h:50-52): those frames take the hook"""
     monkeypatch.setenv("UG_MI355X_VERBOSE", "1")
-    h, r = hook_lib(), T.ref()
+    h, r = LL.ref(hook_lib()), LL.ref()
     av = "yuv422p"
     for (w, h_), cs, rng_ in [((48, 8), 1, 1), ((96, 6), 5, 2)]:
-        frp = T.make_frame(r, av, w, h_, 7, cs, rng_)
-        pitch = r.vc_get_linesize(w, r.get_codec_from_name(uv.encode()))
-        want = T.ref_av_to_uv(frp, av, uv, w, h_, pitch, (0, 8, 16))
-        conv = h.get_av_to_uv_conversion(h.ug_stub_pixfmt_by_name(av.encode()), h.get_codec_from_name(uv.encode()))
-        assert conv
-        dst = np.zeros(pitch * h_ + 64, np.uint8)
-        h.av_to_uv_convert(conv, dst.ctypes.data, frp, pitch, (C.c_int * 3)(0, 8, 16))
-        cp = C.c_void_p(conv)
-        h.av_to_uv_conversion_destroy(C.byref(cp))
-        r.av_frame_free(C.byref(frp))
-        assert np.array_equal(dst[: pitch * h_].reshape(h_, pitch), want), (uv, w, h_, cs, rng_)
+        for layout in ("default", "tight", "offset"):  # tests/lavc_layout.py: the stand-in's own frames, tight lines, planes past an aligned address
+            frp = T.make_frame(r, av, w, h_, 7, cs, rng_) if layout == "default" else LL.make_frame_laid_out(r, av, w, h_, layout, 7, cs, rng_)
+            pitch = r.vc_get_linesize(w, r.get_codec_from_name(uv.encode()))
+            want = T.ref_av_to_uv(frp, av, uv, w, h_, pitch, (0, 8, 16))
+            conv = h.get_av_to_uv_conversion(h.ug_stub_pixfmt_by_name(av.encode()), h.get_codec_from_name(uv.encode()))
+            assert conv
+            dst = np.zeros(pitch * h_ + 64, np.uint8)
+            h.av_to_uv_convert(conv, dst.ctypes.data, frp, pitch, (C.c_int * 3)(0, 8, 16))
+            cp = C.c_void_p(conv)
+            h.av_to_uv_conversion_destroy(C.byref(cp))
+            r.av_frame_free(C.byref(frp))
+            assert np.array_equal(dst[: pitch * h_].reshape(h_, pitch), want), (uv, w, h_, cs, rng_, layout)
     assert f"from_lavc {av} -> {uv} on the device" in capfd.readouterr().err
 
 

@@ -449,6 +449,35 @@ __global__ void k_r12l_to_p210_ayuv64(const Args a)
         }
 }
 
+// r12l_to_gbrpXXle (to_planar.c:380-461) for widths that are no multiple of 8.  The forwarded row (planar_api.hip) stops at `width`; the
+// reference decodes whole groups and so writes up to 7 samples past it -- into the padding of the line where the frame has some.
+template <int DEPTH>
+__global__ void k_r12l_to_gbrp_ragged(const Args a)
+{
+        UG_XY();
+        if (x >= (a.w + 7) / 8 || y >= a.h) return;
+        int c[8][3];
+        r12l_unpack(BUF(const uint8_t, y) + 36 * x, c);
+        uint32_t r[8], g[8], b[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) r[i] = c[i][0], g[i] = c[i][1], b[i] = c[i][2];
+        st16<8>(ROW(uint16_t, 2, y) + 8 * x, r, DEPTH - 12, room16(a.ls[2], 8L * x, 8));
+        st16<8>(ROW(uint16_t, 0, y) + 8 * x, g, DEPTH - 12, room16(a.ls[0], 8L * x, 8));
+        st16<8>(ROW(uint16_t, 1, y) + 8 * x, b, DEPTH - 12, room16(a.ls[1], 8L * x, 8));
+}
+
+// r10k_to_bgr0 :1302-1312 (vc_copyliner10k(dst, src, linesize(RGBA), 16, 8, 0): the top 8 bits of each component) for a plane or line size
+// that is no multiple of four, which the forwarded row (pixfmt_ext.hip) stores as words and refuses: the same pixels, byte by byte
+__global__ void k_r10k_to_bgr0_bytes(const Args a)
+{
+        UG_XY();
+        if (x >= a.w || y >= a.h) return;
+        int r, g, b;
+        r10k_px(BUF(const uint8_t, y) + 4 * x, r, g, b);
+        uint8_t *dst = ROW(uint8_t, 0, y) + 4 * x;
+        dst[0] = (uint8_t) (b >> 2), dst[1] = (uint8_t) (g >> 2), dst[2] = (uint8_t) (r >> 2), dst[3] = 0xff;
+}
+
 // ================================ AVFrame -> UltraGrid codec (from_lavc_vid_conv.c) ================================================
 // a.d / a.ls = the decoder's planes, a.buf / a.pitch = output
 
@@ -1184,7 +1213,7 @@ const Conv kToAv[] = {
         { "R10k", "gbrp10le", k_r10k_to_gbrpXX<10>, NX_W, NY_H, 0, F_NONE, nullptr, 3 },
         { "R10k", "gbrp16le", k_r10k_to_gbrpXX<16>, NX_W, NY_H, 0, F_NONE, nullptr, 3 },
         { "R10k", "x2rgb10le", k_r10k_to_x2rgb10le, NX_W, NY_H, 0, F_NONE, nullptr, 1 },
-        { "R10k", "bgr0", nullptr, NX_W, NY_H, 0, F_PIXFMT_R10K_BGR0, nullptr, 1 },
+        { "R10k", "bgr0", k_r10k_to_bgr0_bytes, NX_W, NY_H, 0, F_PIXFMT_R10K_BGR0, nullptr, 1 }, // (the kernel: planes off a multiple of four)
         { "R12L", "yuv444p10le", k_r12l_to_yuv<10, false>, NX_W8UP, NY_H, 10, F_NONE, nullptr, 3 },
         { "R12L", "yuv444p12le", k_r12l_to_yuv<12, false>, NX_W8UP, NY_H, 12, F_NONE, nullptr, 3 },
         { "R12L", "yuv444p16le", k_r12l_to_yuv<16, false>, NX_W8UP, NY_H, 16, F_NONE, nullptr, 3 },
@@ -1193,8 +1222,8 @@ const Conv kToAv[] = {
         { "R12L", "yuv422p16le", k_r12l_to_yuv<16, true>, NX_W8UP, NY_H, 16, F_NONE, nullptr, 3 },
         { "R12L", "p210le", k_r12l_to_p210_ayuv64<false>, NX_W8UP, NY_H, 10, F_NONE, nullptr, 2 },
         { "R12L", "ayuv64le", k_r12l_to_p210_ayuv64<true>, NX_W8UP, NY_H, 16, F_NONE, nullptr, 1 },
-        { "R12L", "gbrp12le", nullptr, NX_W, NY_H, 0, F_TO_PLANAR, "r12l_to_gbrp12le", 3 },
-        { "R12L", "gbrp16le", nullptr, NX_W, NY_H, 0, F_TO_PLANAR, "r12l_to_gbrp16le", 3 },
+        { "R12L", "gbrp12le", k_r12l_to_gbrp_ragged<12>, NX_W8UP, NY_H, 0, F_TO_PLANAR, "r12l_to_gbrp12le", 3 }, // (the kernel: width % 8 != 0)
+        { "R12L", "gbrp16le", k_r12l_to_gbrp_ragged<16>, NX_W8UP, NY_H, 0, F_TO_PLANAR, "r12l_to_gbrp16le", 3 },
         { "RG48", "yuv444p10le", k_rgb_to_yuv444pXX<16, 10>, NX_W, NY_H, 10, F_NONE, nullptr, 3 },
         { "RG48", "yuv444p12le", k_rgb_to_yuv444pXX<16, 12>, NX_W, NY_H, 12, F_NONE, nullptr, 3 },
         { "RG48", "yuv444p16le", k_rgb_to_yuv444pXX<16, 16>, NX_W, NY_H, 16, F_NONE, nullptr, 3 },
@@ -1338,7 +1367,7 @@ int launch(const Conv &c, const Args &a, hipStream_t st)
 int frame_align(const char *av)
 {
         if (strstr(av, "xv30") || strstr(av, "vuy") || strstr(av, "x2rgb")) return 4;
-        if (strstr(av, "10le") || strstr(av, "12le") || strstr(av, "16le") || strstr(av, "y21") || strstr(av, "ayuv64")) return 2;
+        if (strstr(av, "10le") || strstr(av, "12le") || strstr(av, "16le") || strstr(av, "48le") || strstr(av, "y21") || strstr(av, "ayuv64")) return 2;
         return 1;
 }
 
@@ -1440,6 +1469,7 @@ int ug_hip_uv_to_av(const char *uv_codec, const char *av_pixfmt, const void *in_
         case F_I422:
                 return ug_hip_uyvy_to_i422(in_data, 0, out->data[0], out->linesize[0], out->data[1], out->linesize[1], out->data[2], out->linesize[2], w, h, stream);
         case F_TO_PLANAR: {
+                if (c->kernel && w % 8) break; // R12L -> gbrp: the last group of a ragged line runs on into the padding (k_r12l_to_gbrp_ragged)
                 ug_to_planar_data d = {};
                 d.width = w, d.height = h, d.in_data = in_data;
                 for (int i = 0; i < c->min_planes; i++) d.out_data[i] = out->data[i], d.out_linesize[i] = (unsigned) out->linesize[i];
@@ -1451,6 +1481,7 @@ int ug_hip_uv_to_av(const char *uv_codec, const char *av_pixfmt, const void *in_
                 return UG_HIP_SUCCESS;
         }
         case F_PIXFMT_R10K_BGR0: // r10k_to_bgr0 :1302-1312: vc_copyliner10k(dst, src, linesize(RGBA), 16, 8, 0)
+                if (((uintptr_t) out->data[0] | (uintptr_t) out->linesize[0]) & 3) break; // k_r10k_to_bgr0_bytes
                 return ug_hip_pixfmt_convert(UG_PF_R10K, UG_PF_RGBA, in_data, out->data[0], w, h, 0, out->linesize[0], 16, 8, 0, stream);
         case F_PIXFMT_RGB_BGR0: // rgb_to_bgr0, to_lavc_vid_conv.c:1291-1300: vc_copylineRGBtoRGBA(dst, src, linesize(RGBA), 16, 8, 0)
                 return ug_hip_pixfmt_convert(UG_PF_RGB, UG_PF_RGBA, in_data, out->data[0], w, h, 0, out->linesize[0], 16, 8, 0, stream);

@@ -142,6 +142,8 @@ __global__ __launch_bounds__(256) void uyvy_to_i422_kernel(const uint8_t *__rest
 // 16 * (width / 16) pixels of a line pair go through _mm_avg_epu8 = (a + b + 1) >> 1, the rest through the scalar tail
 // (a + b) / 2 -- the result depends on the width, and this kernel reproduces that dependence (vec_px = 16 * (width / 16);
 // vec_px = 0 gives the build without SSE3).  One lane = one pixel pair of a line pair; odd height: the last line pairs with itself.
+// BYTES: a CbCr plane at an odd address or with an odd line size (the reference stores bytes, to_planar.c:285-291) takes two byte stores.
+template <bool BYTES>
 __global__ __launch_bounds__(256) void uyvy_to_nv12_kernel(const uint8_t *__restrict__ src, long src_pitch, uint8_t *__restrict__ py, long y_pitch,
                                                           uint8_t *__restrict__ pc, long c_pitch, int width, int height, int vec_px)
 {
@@ -152,7 +154,12 @@ __global__ __launch_bounds__(256) void uyvy_to_nv12_kernel(const uint8_t *__rest
         const uint32_t a = *(const uint32_t *) (src + (long) y0 * src_pitch + 4 * i), b = *(const uint32_t *) (src + (long) y1 * src_pitch + 4 * i);
         const uint32_t rnd = 2 * i < vec_px ? 1 : 0;
         const uint32_t cb = ((a & 0xff) + (b & 0xff) + rnd) >> 1, cr = (((a >> 16) & 0xff) + ((b >> 16) & 0xff) + rnd) >> 1;
-        *(uint16_t *) (pc + (long) cy * c_pitch + 2 * i) = (uint16_t) (cb | cr << 8);
+        if (BYTES) {
+                uint8_t *c = pc + (long) cy * c_pitch + 2 * i;
+                c[0] = (uint8_t) cb, c[1] = (uint8_t) cr;
+        } else {
+                *(uint16_t *) (pc + (long) cy * c_pitch + 2 * i) = (uint16_t) (cb | cr << 8);
+        }
         const bool second = 2 * i + 1 < width; // odd width: the last pair has one luma sample (to_planar.c:294-299)
         uint8_t *d0 = py + (long) y0 * y_pitch + 2 * i, *d1 = py + (long) y1 * y_pitch + 2 * i;
         d0[0] = (uint8_t) (a >> 8);
@@ -327,7 +334,7 @@ int ug_hip_uyvy_to_nv12(const void *src, int src_pitch, void *y, int y_pitch, vo
                         ug_hip_stream_t stream)
 {
         if (!ug::dims_ok(width, height)) return ug::refuse_size("ug_hip_uyvy_to_nv12");
-        if (!src || !y || !cbcr || width <= 0 || height <= 0 || (height + 7) / 8 > 65535 || (3 & (uintptr_t) src) || (1 & (uintptr_t) cbcr)) {
+        if (!src || !y || !cbcr || width <= 0 || height <= 0 || (height + 7) / 8 > 65535 || (3 & (uintptr_t) src)) {
                 ug::set_last_error_msg("ug_hip_uyvy_to_nv12: bad arguments");
                 return UG_HIP_EINVAL;
         }
@@ -336,8 +343,8 @@ int ug_hip_uyvy_to_nv12(const void *src, int src_pitch, void *y, int y_pitch, vo
         if (!y_pitch) y_pitch = width;
         if (!cbcr_pitch) cbcr_pitch = 2 * cw;
         if (!ug::planes_ok(height, { src_pitch, y_pitch, cbcr_pitch })) return ug::refuse_size("ug_hip_uyvy_to_nv12");
-        if ((src_pitch & 3) || (cbcr_pitch & 1)) {
-                ug::set_last_error_msg("ug_hip_uyvy_to_nv12: source pitch must be a multiple of 4, CbCr pitch of 2");
+        if (src_pitch & 3) {
+                ug::set_last_error_msg("ug_hip_uyvy_to_nv12: source pitch must be a multiple of 4");
                 return UG_HIP_EINVAL;
         }
         const dim3 block(64, 4);
@@ -349,8 +356,9 @@ int ug_hip_uyvy_to_nv12(const void *src, int src_pitch, void *y, int y_pitch, vo
                 return UG_HIP_SUCCESS;
         }
         const dim3 grid((unsigned) ((cw + 63) / 64), (unsigned) (((height + 1) / 2 + 3) / 4));
-        hipLaunchKernelGGL(uyvy_to_nv12_kernel, grid, block, 0, (hipStream_t) stream, (const uint8_t *) src, (long) src_pitch, (uint8_t *) y,
-                           (long) y_pitch, (uint8_t *) cbcr, (long) cbcr_pitch, width, height, 16 * (width / 16));
+        const auto kernel = (((uintptr_t) cbcr | (uintptr_t) cbcr_pitch) & 1) ? uyvy_to_nv12_kernel<true> : uyvy_to_nv12_kernel<false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t) stream, (const uint8_t *) src,
+                           (long) src_pitch, (uint8_t *) y, (long) y_pitch, (uint8_t *) cbcr, (long) cbcr_pitch, width, height, 16 * (width / 16));
         UG_HIP_LAUNCH_CHECK();
         return UG_HIP_SUCCESS;
 }
