@@ -18,16 +18,16 @@ cp "$M/ug_codec_map.h" "$M/mi355x_frame_sharder.h" "$M/mi355x_tile_encoder.h" "$
 cp "$M/vdecompress_dxt_mi355x.c"             "$UG/src/video_decompress/dxt_mi355x.c"
 cp "$M/vdecompress_jpeg_mi355x.c"            "$UG/src/video_decompress/jpeg_mi355x.c"
 cp "$M/vdecompress_jpeg_to_dxt_mi355x.c"     "$UG/src/video_decompress/jpeg_to_dxt_mi355x.c"
-cp "$M/mi355x_receiver.h"                    "$UG/src/video_decompress/"
+cp "$M/mi355x_receiver.h" "$M/mi355x_gpu_state.h" "$UG/src/video_decompress/"
 cp "$M/lavc_conv_mi355x.cpp"                 "$UG/src/libavcodec/lavc_conv_mi355x.cpp"
 cp "$M/ldgm_gpu_mi355x.cpp"                  "$UG/src/rtp/ldgm_gpu_mi355x.cpp"
 cp "$M/mi355x_receiver.h"                    "$UG/src/rtp/"
 cp "$M/vo_pp_scale_mi355x.c"                "$UG/src/vo_postprocess/scale_mi355x.c"
 cp "$M/vo_pp_deinterlace_mi355x.c"          "$UG/src/vo_postprocess/deinterlace_mi355x.c"
 cp "$M/vo_pp_compose_mi355x.c"              "$UG/src/vo_postprocess/compose_mi355x.c"
-cp "$M/mi355x_receiver.h" "$M/ug_codec_map.h" "$UG/src/vo_postprocess/"
+cp "$M/mi355x_receiver.h" "$M/mi355x_gpu_state.h" "$M/ug_codec_map.h" "$UG/src/vo_postprocess/"
 cp "$M/capture_filter_pixel_mi355x.c"       "$UG/src/capture_filter/pixel_mi355x.c"
-cp "$M/mi355x_receiver.h" "$M/ug_codec_map.h" "$UG/src/capture_filter/"
+cp "$M/mi355x_receiver.h" "$M/mi355x_gpu_state.h" "$M/ug_codec_map.h" "$UG/src/capture_filter/"
 if grep -q "found_ug_mi355x" "$UG/configure.ac"; then
         echo "configure.ac is patched already"
 else

@@ -51,7 +51,7 @@ def test_installed_module_compiles_where_install_put_it(tmp_path):
     subprocess.run(["sh", os.path.join(ROOT, "integration", "install.sh"), str(ug)], check=True, capture_output=True)
     src = ug / "src" / "vo_postprocess" / "deinterlace_mi355x.c"
     assert src.read_bytes() == open(os.path.join(ROOT, "ultragrid_amd", "module", "vo_pp_deinterlace_mi355x.c"), "rb").read()
-    for h in ("mi355x_receiver.h", "ug_codec_map.h"):
+    for h in ("mi355x_receiver.h", "mi355x_gpu_state.h", "ug_codec_map.h"):
         assert (ug / "src" / "vo_postprocess" / h).exists()
     (tmp_path / "config.h").write_text("")
     obj = tmp_path / "m.o"

@@ -63,6 +63,7 @@ def _compile(tmp_path, defines):
         subprocess.run(["sh", os.path.join(ROOT, "integration", "install.sh"), str(ug)], check=True, capture_output=True)
         assert (ug / "src" / "vo_postprocess" / "scale_mi355x.c").read_bytes() == open(os.path.join(ROOT, "ultragrid_amd", "module", "vo_pp_scale_mi355x.c"), "rb").read()
         assert (ug / "src" / "vo_postprocess" / "mi355x_receiver.h").exists()
+        assert (ug / "src" / "vo_postprocess" / "mi355x_gpu_state.h").exists()
     cfg = tmp_path / ("cfg_" + "_".join(defines or ["none"]))
     cfg.mkdir(exist_ok=True)
     (cfg / "config.h").write_text("".join(f"#define {d} 1\n" for d in defines))

@@ -2,7 +2,8 @@
 `make -C ultragrid_amd/module sanitize` into oracle/_ref/ and run here in the CPU suite:
   ug_sharder_test_tsan   the frame sharder (mi355x_frame_sharder.h) + the reference's video_frame / vf_split objects under ThreadSanitizer
   ug_jpeg_parser_asan    the host half of csrc/jpeg_decode.hip -- the header parser that meets network bytes -- under ASan + UBSan
-  ug_dec_harness_asan    the three plain-C decompress shims behind the reference's video_decompress.c under ASan + UBSan"""
+  ug_dec_harness_asan    the three plain-C decompress shims behind the reference's video_decompress.c under ASan + UBSan
+  ug_gpu_state_test[_asan]  mi355x_gpu_state.h (what the C filter and decoder modules share) against a host-memory stand-in for the runtime"""
 import io
 import os
 import subprocess
@@ -69,3 +70,17 @@ def test_decompress_shims_under_address_and_ub_sanitizer(tmp_path):
     src.write_bytes(b.getvalue())
     r = subprocess.run([DEC, "JPEG", "UYVY", str(w), str(h), str(src), str(dst)], capture_output=True, text=True, timeout=120, env=env)
     _clean(r)
+
+
+@pytest.mark.parametrize("name", ["ug_gpu_state_test", "ug_gpu_state_test_asan"])
+def test_gpu_state_core_against_a_host_stand_in(name):
+    """Device rotation, a malformed list, a stream that cannot be made, grow-only buffers with an allocation that fails, the synchronising tail
+    and teardown (module/ug_gpu_state_test.c): no GPU, no HIP call -- the program defines the nine ug_hip_* functions itself."""
+    exe = os.path.join(REF, name)
+    if not os.path.exists(exe):
+        pytest.skip(f"oracle/_ref/{name} not built (needs /root/reference)")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1 exitcode=66", UBSAN_OPTIONS="print_stacktrace=1 halt_on_error=1")
+    env.pop("UG_PARAM", None)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=env)
+    out = _clean(r)
+    assert r.returncode == 0 and out.strip() == "OK", out[-3000:]

@@ -43,7 +43,7 @@
 #include "video_frame.h"
 #include "vo_postprocess/capture_filter_wrapper.h"
 
-#include "mi355x_receiver.h"
+#include "mi355x_gpu_state.h"
 #include "ug_codec_map.h"
 
 #define MOD_NAME "[pixel filter MI355X] "
@@ -59,13 +59,10 @@ struct state_pxf_mi355x {
         bool            check_bounds;
         int             out_depth;        ///< gamma: 0, 8 or 16 (0 means keep)
         unsigned char  *luts;             ///< gamma: the four host tables back to back (8->8, 8->16, 16->8, 16->16)
-        void           *luts_dev;
+        struct mi355x_buf luts_dev;
         void           *vo_pp_out_buffer; ///< buffer to write to if we use vo_pp wrapper (otherwise unused)
-        int             device;
-        ug_hip_stream_t stream;
-        char           *host_in;          ///< pinned
-        void           *dev_in, *dev_out;
-        size_t          in_cap, out_cap;
+        struct mi355x_gpu gpu;
+        struct mi355x_buf host_in, dev_in, dev_out; ///< host_in: pinned
 };
 
 static unsigned pxf_mi355x_state_count; // the states of this process take the listed devices in turn
@@ -122,15 +119,11 @@ static int parse_matrix(struct state_pxf_mi355x *s, const char *cfg)
 static void done(void *state)
 {
         struct state_pxf_mi355x *s = state;
-        if (s->stream != NULL || s->luts_dev != NULL || s->host_in != NULL) {
-                ug_hip_set_device(s->device);
-                if (s->stream) ug_hip_stream_sync(s->stream);
-                if (s->host_in) ug_hip_free_host(s->host_in);
-                if (s->dev_in) ug_hip_free(s->dev_in);
-                if (s->dev_out) ug_hip_free(s->dev_out);
-                if (s->luts_dev) ug_hip_free(s->luts_dev);
-                if (s->stream) ug_hip_stream_destroy(s->stream);
-        }
+        mi355x_gpu_close(&s->gpu); // (nothing on a state whose stream was never made: its bufs are empty.  The device stays the current one)
+        mi355x_buf_release(&s->host_in);
+        mi355x_buf_release(&s->dev_in);
+        mi355x_buf_release(&s->dev_out);
+        mi355x_buf_release(&s->luts_dev);
         free(s->luts);
         free(s);
 }
@@ -183,10 +176,8 @@ static int init_common(enum pxf_kind kind, const char *cfg, void **state)
                         return -1;
                 }
         }
-        s->device = mi355x_next_state_device(&pxf_mi355x_state_count, MOD_NAME);
-        if (s->device < 0 || ug_hip_set_device(s->device) != UG_HIP_SUCCESS || ug_hip_stream_create(&s->stream) != UG_HIP_SUCCESS) {
-                if (s->device >= 0) MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
-                s->stream = NULL;
+        s->host_in.pinned = true;
+        if (!mi355x_gpu_open(&s->gpu, &pxf_mi355x_state_count, MOD_NAME)) {
                 done(s);
                 return -1;
         }
@@ -197,23 +188,9 @@ static int init_common(enum pxf_kind kind, const char *cfg, void **state)
 /// the buffers follow the frame: at least in_len / out_len bytes
 static bool reserve(struct state_pxf_mi355x *s, size_t in_len, size_t out_len)
 {
-        bool ok = true;
-        if (in_len > s->in_cap) {
-                if (s->host_in) ug_hip_free_host(s->host_in);
-                if (s->dev_in) ug_hip_free(s->dev_in);
-                s->host_in = NULL, s->dev_in = NULL, s->in_cap = 0;
-                ok = ug_hip_malloc_host((void **) &s->host_in, in_len) == UG_HIP_SUCCESS && ug_hip_malloc(&s->dev_in, in_len) == UG_HIP_SUCCESS;
-                if (ok) s->in_cap = in_len;
-        }
-        if (ok && out_len > s->out_cap) {
-                if (s->dev_out) ug_hip_free(s->dev_out);
-                s->dev_out = NULL, s->out_cap = 0;
-                ok = ug_hip_malloc(&s->dev_out, out_len) == UG_HIP_SUCCESS;
-                if (ok) s->out_cap = out_len;
-        }
-        if (ok && s->kind == K_GAMMA && s->luts_dev == NULL) {
-                ok = ug_hip_malloc(&s->luts_dev, LUTS_LEN) == UG_HIP_SUCCESS &&
-                     ug_hip_memcpy(s->luts_dev, s->luts, LUTS_LEN, UG_HIP_MEMCPY_HOST_TO_DEVICE) == UG_HIP_SUCCESS;
+        bool ok = mi355x_buf_reserve(&s->host_in, in_len) && mi355x_buf_reserve(&s->dev_in, in_len) && mi355x_buf_reserve(&s->dev_out, out_len);
+        if (ok && s->kind == K_GAMMA && s->luts_dev.ptr == NULL) {
+                ok = mi355x_buf_reserve(&s->luts_dev, LUTS_LEN) && ug_hip_memcpy(s->luts_dev.ptr, s->luts, LUTS_LEN, UG_HIP_MEMCPY_HOST_TO_DEVICE) == UG_HIP_SUCCESS;
         }
         if (!ok) MSG(ERROR, "cannot allocate the frame buffers: %s\n", ug_hip_last_error_string());
         return ok;
@@ -228,32 +205,24 @@ static bool run_gpu(struct state_pxf_mi355x *s, const struct video_frame *in, st
                 MSG(ERROR, "frame shorter than %zu lines of %zu bytes\n", rows, in_line);
                 return false;
         }
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
-                return false;
-        }
-        if (!reserve(s, in_len, out_len)) {
+        if (!mi355x_gpu_enter(&s->gpu) || !reserve(s, in_len, out_len)) {
                 return false;
         }
         struct ug_pixel_filter_desc d = {
-                .src = s->dev_in, .dst = s->dev_out, .op = ops[s->kind], .format = ug_pixfmt_from_codec(in->color_spec),
+                .src = s->dev_in.ptr, .dst = s->dev_out.ptr, .op = ops[s->kind], .format = ug_pixfmt_from_codec(in->color_spec),
                 .out_format = ug_pixfmt_from_codec(out->color_spec), .width = (int) in->tiles[0].width, .lines = (int) rows, .frames = 1,
                 .clamp = s->check_bounds,
         };
         memcpy(d.matrix, s->matrix, sizeof d.matrix);
         if (s->kind == K_GAMMA) {
                 const bool in16 = in->color_spec == RG48, out16 = out->color_spec == RG48;
-                d.lut_dev = (char *) s->luts_dev + (in16 ? (out16 ? LUT16_OFF : LUT16_8_OFF) : (out16 ? LUT8_16_OFF : LUT8_OFF));
+                d.lut_dev = (char *) s->luts_dev.ptr + (in16 ? (out16 ? LUT16_OFF : LUT16_8_OFF) : (out16 ? LUT8_16_OFF : LUT8_OFF));
         }
-        memcpy(s->host_in, in->tiles[0].data, in_len);
-        bool ok = ug_hip_upload_ordered_ex(s->device, s->dev_in, s->host_in, in_len, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream, 0) == UG_HIP_SUCCESS &&
-                  ug_hip_pixel_filter(&d, s->stream) == UG_HIP_SUCCESS &&
-                  ug_hip_download_2d_ordered_ex(s->device, out->tiles[0].data, out_line, s->dev_out, out_line, out_line, rows, s->stream, 0) == UG_HIP_SUCCESS;
-        if (!ok) MSG(ERROR, "%s failed: %s\n", kind_names[s->kind], ug_hip_last_error_string());
-        // whatever was queued has finished when this returns, also after a failure
-        const bool synced = ug_hip_stream_sync(s->stream) == UG_HIP_SUCCESS;
-        if (ok && !synced) MSG(ERROR, "stream sync failed: %s\n", ug_hip_last_error_string());
-        return ok && synced;
+        memcpy(s->host_in.ptr, in->tiles[0].data, in_len);
+        const bool ok = ug_hip_upload_ordered_ex(s->gpu.device, s->dev_in.ptr, s->host_in.ptr, in_len, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->gpu.stream, 0) == UG_HIP_SUCCESS &&
+                        ug_hip_pixel_filter(&d, s->gpu.stream) == UG_HIP_SUCCESS &&
+                        ug_hip_download_2d_ordered_ex(s->gpu.device, out->tiles[0].data, out_line, s->dev_out.ptr, out_line, out_line, rows, s->gpu.stream, 0) == UG_HIP_SUCCESS;
+        return mi355x_gpu_finish(&s->gpu, ok, kind_names[s->kind]);
 }
 
 static struct video_frame *filter(void *state, struct video_frame *in)

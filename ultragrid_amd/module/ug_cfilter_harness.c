@@ -37,30 +37,8 @@
 #include "video_frame.h"
 #include "vo_postprocess.h"
 
-/* what host.cpp would provide (the reference's tools/ug_stub.c answers NULL to every key; this one answers from UG_PARAM) */
-static char *uv_argv_store[] = { "ug_cfilter_harness", NULL };
-char **uv_argv = uv_argv_store;
-void register_param(const char *param, const char *doc) { (void) param, (void) doc; }
-bool tok_in_argv(char **argv, const char *tok) { (void) argv, (void) tok; return false; }
-void set_commandline_param(const char *key, const char *val) { (void) key, (void) val; }
-const char *get_commandline_param(const char *key)
-{
-        static char vals[8][128];
-        static int slot;
-        const char *p = getenv("UG_PARAM");
-        const size_t kl = strlen(key);
-        while (p != NULL && *p != '\0') {
-                const char *end = strchr(p, ',');
-                const size_t len = end ? (size_t) (end - p) : strlen(p);
-                if (len >= kl && strncmp(p, key, kl) == 0 && (len == kl || p[kl] == '=')) {
-                        char *v = vals[slot++ % 8];
-                        snprintf(v, sizeof vals[0], "%.*s", len > kl ? (int) (len - kl - 1) : 0, p + kl + (len > kl ? 1 : 0));
-                        return v;
-                }
-                p = end ? end + 1 : NULL;
-        }
-        return NULL;
-}
+#define UG_HARNESS_NAME "ug_cfilter_harness"
+#include "ug_harness_host.h" /* what host.cpp would provide; get_commandline_param answers from UG_PARAM */
 
 /* -Wl,--wrap=malloc (see UG_CFILTER_PAD above) */
 void *__real_malloc(size_t size);
@@ -100,13 +78,6 @@ static void report(const char *name, int i, struct video_desc d, unsigned data_l
 {
         printf("%s frame %d %u %u %s %d %.3f %u %u ret=%s\n", name, i, d.width, d.height, get_codec_name(d.color_spec), (int) d.interlacing, d.fps, d.tile_count,
                data_len, ret);
-}
-
-static double now_ms(void)
-{
-        struct timespec t;
-        clock_gettime(CLOCK_MONOTONIC, &t);
-        return (double) t.tv_sec * 1e3 + (double) t.tv_nsec / 1e6;
 }
 
 static int run_one(const char *name, int argc, char **argv)

@@ -31,42 +31,8 @@
 #include "video_frame.h"
 #include "vo_postprocess.h"
 
-/* what host.cpp would provide (the reference's tools/ug_stub.c answers NULL to every key; this one answers from UG_PARAM and from what
- * set_commandline_param stored) */
-static char *uv_argv_store[] = { "ug_deint_harness", NULL };
-char **uv_argv = uv_argv_store;
-static char set_keys[8][64], set_vals[8][128];
-static int set_count;
-void register_param(const char *param, const char *doc) { (void) param, (void) doc; }
-bool tok_in_argv(char **argv, const char *tok) { (void) argv, (void) tok; return false; }
-void set_commandline_param(const char *key, const char *val)
-{
-        if (set_count < 8) {
-                snprintf(set_keys[set_count], sizeof set_keys[0], "%s", key);
-                snprintf(set_vals[set_count++], sizeof set_vals[0], "%s", val);
-        }
-}
-const char *get_commandline_param(const char *key)
-{
-        static char vals[8][128];
-        static int slot;
-        for (int i = 0; i < set_count; i++) {
-                if (strcmp(set_keys[i], key) == 0) return set_vals[i];
-        }
-        const char *p = getenv("UG_PARAM");
-        const size_t kl = strlen(key);
-        while (p != NULL && *p != '\0') {
-                const char *end = strchr(p, ',');
-                const size_t len = end ? (size_t) (end - p) : strlen(p);
-                if (len >= kl && strncmp(p, key, kl) == 0 && (len == kl || p[kl] == '=')) {
-                        char *v = vals[slot++ % 8];
-                        snprintf(v, sizeof vals[0], "%.*s", len > kl ? (int) (len - kl - 1) : 0, p + kl + (len > kl ? 1 : 0));
-                        return v;
-                }
-                p = end ? end + 1 : NULL;
-        }
-        return NULL;
-}
+#define UG_HARNESS_NAME "ug_deint_harness"
+#include "ug_harness_host.h" /* what host.cpp would provide; get_commandline_param answers from UG_PARAM */
 
 static bool write_file(const char *prefix, const char *name, int i, int k, const char *data, size_t len)
 {

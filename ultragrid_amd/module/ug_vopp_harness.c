@@ -27,29 +27,8 @@
 #include "video_frame.h"
 #include "vo_postprocess.h"
 
-/* what host.cpp would provide (the reference's tools/ug_stub.c answers NULL to every key; this one answers from UG_PARAM) */
-static char *uv_argv_store[] = { "ug_vopp_harness", NULL };
-char **uv_argv = uv_argv_store;
-void register_param(const char *param, const char *doc) { (void) param, (void) doc; }
-bool tok_in_argv(char **argv, const char *tok) { (void) argv, (void) tok; return false; }
-const char *get_commandline_param(const char *key)
-{
-        static char vals[8][128];
-        static int slot;
-        const char *p = getenv("UG_PARAM");
-        const size_t kl = strlen(key);
-        while (p != NULL && *p != '\0') {
-                const char *end = strchr(p, ',');
-                const size_t len = end ? (size_t) (end - p) : strlen(p);
-                if (len >= kl && strncmp(p, key, kl) == 0 && (len == kl || p[kl] == '=')) {
-                        char *v = vals[slot++ % 8];
-                        snprintf(v, sizeof vals[0], "%.*s", len > kl ? (int) (len - kl - 1) : 0, p + kl + (len > kl ? 1 : 0));
-                        return v;
-                }
-                p = end ? end + 1 : NULL;
-        }
-        return NULL;
-}
+#define UG_HARNESS_NAME "ug_vopp_harness"
+#include "ug_harness_host.h" /* what host.cpp would provide; get_commandline_param answers from UG_PARAM */
 
 static int run(int argc, char **argv)
 {

@@ -23,7 +23,7 @@
 #include "video_codec.h"
 #include "video_decompress.h"
 
-#include "mi355x_receiver.h"
+#include "mi355x_gpu_state.h"
 
 #define MOD_NAME "[DXT MI355X dec] "
 #define MI355X_MAX_BANDS 16
@@ -34,11 +34,10 @@ struct state_decompress_dxt_mi355x {
         codec_t           out_codec;
         ug_dxt_t          in_fmt;
         ug_pixfmt_t       out_fmt;
-        int               device; ///< --param mi355x-device / -D (mi355x_receiver.h)
+        struct mi355x_gpu gpu;
         int               bands_param; ///< --param mi355x-bands (MI355X_AUTO_BANDS: chosen at reconfigure by the size of the frame)
         int               bands;
-        ug_hip_stream_t   stream;
-        void             *dev_in, *dev_out;
+        struct mi355x_buf dev_in, dev_out;
         size_t            in_len, out_len;
         bool              configured;
         // the band pipeline's second thread (see decode_in_bands): downloads band k while the caller's thread uploads band k + 1
@@ -66,25 +65,20 @@ static void *dxt_mi355x_decompress_init(void)
         if (s == NULL) {
                 return NULL;
         }
-        s->device = mi355x_next_state_device(&dxt_mi355x_state_count, MOD_NAME);
-        s->bands_param = mi355x_receiver_bands(MI355X_AUTO_BANDS);
-        pthread_mutex_init(&s->lock, NULL);
-        pthread_cond_init(&s->cv, NULL);
-        if (s->device < 0 || ug_hip_set_device(s->device) != UG_HIP_SUCCESS || ug_hip_stream_create(&s->stream) != UG_HIP_SUCCESS) {
-                if (s->device >= 0) MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
-                pthread_cond_destroy(&s->cv);
-                pthread_mutex_destroy(&s->lock);
+        if (!mi355x_gpu_open(&s->gpu, &dxt_mi355x_state_count, MOD_NAME)) {
                 free(s);
                 return NULL;
         }
+        s->bands_param = mi355x_receiver_bands(MI355X_AUTO_BANDS);
+        pthread_mutex_init(&s->lock, NULL);
+        pthread_cond_init(&s->cv, NULL);
         return s;
 }
 
 static void release_buffers(struct state_decompress_dxt_mi355x *s)
 {
-        if (s->dev_in) ug_hip_free(s->dev_in);
-        if (s->dev_out) ug_hip_free(s->dev_out);
-        s->dev_in = s->dev_out = NULL;
+        mi355x_buf_release(&s->dev_in);
+        mi355x_buf_release(&s->dev_out);
         s->configured = false;
 }
 
@@ -92,8 +86,7 @@ static int dxt_mi355x_decompress_reconfigure(void *state, struct video_desc desc
                                              int pitch, codec_t out_codec)
 {
         struct state_decompress_dxt_mi355x *s = state;
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
+        if (!mi355x_gpu_enter(&s->gpu)) {
                 return false;
         }
         release_buffers(s);
@@ -136,14 +129,14 @@ static int dxt_mi355x_decompress_reconfigure(void *state, struct video_desc desc
         // between the two threads costs more than the overlap gives.
         const size_t traffic = s->in_len + s->out_len;
         s->bands = s->bands_param != MI355X_AUTO_BANDS ? s->bands_param : (traffic >= ((size_t) 64 << 20) ? 4 : (traffic >= ((size_t) 16 << 20) ? 2 : 1));
-        if (s->in_len == 0 || ug_hip_malloc(&s->dev_in, s->in_len) != UG_HIP_SUCCESS || ug_hip_malloc(&s->dev_out, s->out_len + 64) != UG_HIP_SUCCESS) {
+        if (s->in_len == 0 || !mi355x_buf_reserve(&s->dev_in, s->in_len) || !mi355x_buf_reserve(&s->dev_out, s->out_len + 64)) {
                 MSG(ERROR, "Could not allocate device buffers: %s\n", ug_hip_last_error_string());
                 release_buffers(s);
                 return false;
         }
         // a short (corrupted) frame uploads only the bytes that arrived and decodes the whole block grid: what did not arrive must not be
         // whatever the allocation held -- start from all-zero blocks (black), later frames leave the previous picture there
-        if (ug_hip_memset_async(s->dev_in, 0, s->in_len, s->stream) != UG_HIP_SUCCESS || ug_hip_stream_sync(s->stream) != UG_HIP_SUCCESS) {
+        if (ug_hip_memset_async(s->dev_in.ptr, 0, s->in_len, s->gpu.stream) != UG_HIP_SUCCESS || ug_hip_stream_sync(s->gpu.stream) != UG_HIP_SUCCESS) {
                 MSG(ERROR, "Could not clear the device input buffer: %s\n", ug_hip_last_error_string());
                 release_buffers(s);
                 return false;
@@ -171,8 +164,8 @@ static void *downloader_thread(void *arg)
                 const struct band_job job = s->job;
                 pthread_mutex_unlock(&s->lock);
                 const size_t ls = (size_t) vc_get_linesize(s->desc.width, s->out_codec);
-                const bool ok = ug_hip_set_device(s->device) == UG_HIP_SUCCESS && ug_hip_stream_wait_event(s->down, s->band_done[k]) == UG_HIP_SUCCESS &&
-                                mi355x_download_picture(job.dst + (size_t) job.r0[k] * s->pitch, (size_t) s->pitch, (char *) s->dev_out + (size_t) job.r0[k] * ls, ls,
+                const bool ok = ug_hip_set_device(s->gpu.device) == UG_HIP_SUCCESS && ug_hip_stream_wait_event(s->down, s->band_done[k]) == UG_HIP_SUCCESS &&
+                                mi355x_download_picture(job.dst + (size_t) job.r0[k] * s->pitch, (size_t) s->pitch, (char *) s->dev_out.ptr + (size_t) job.r0[k] * ls, ls,
                                                         (size_t) (job.r0[k + 1] - job.r0[k]), s->down) == UG_HIP_SUCCESS &&
                                 (k + 1 < job.bands || ug_hip_stream_sync(s->down) == UG_HIP_SUCCESS); // (the last band: the picture is complete when this returns)
                 pthread_mutex_lock(&s->lock);
@@ -213,9 +206,9 @@ static bool decode_in_bands(struct state_decompress_dxt_mi355x *s, unsigned char
         const size_t block_row = s->in_len / (size_t) ((h + 3) / 4); // bytes of one row of blocks
         const bool cuttable = (linesize & 15) == 0 && h >= 64 && s->bands > 1;
         if (!cuttable || !start_downloader(s)) { // one after the other, on the caller's thread and the state's stream
-                const bool ok = ug_hip_memcpy_async(s->dev_in, buffer, n, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream) == UG_HIP_SUCCESS &&
-                                ug_hip_dxt_decode(s->in_fmt, s->out_fmt, s->dev_in, s->dev_out, w, h, 0, s->rshift, s->gshift, s->bshift, s->stream) == UG_HIP_SUCCESS &&
-                                mi355x_download_picture(dst, (size_t) s->pitch, s->dev_out, linesize, (size_t) h, s->stream) == UG_HIP_SUCCESS;
+                const bool ok = ug_hip_memcpy_async(s->dev_in.ptr, buffer, n, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->gpu.stream) == UG_HIP_SUCCESS &&
+                                ug_hip_dxt_decode(s->in_fmt, s->out_fmt, s->dev_in.ptr, s->dev_out.ptr, w, h, 0, s->rshift, s->gshift, s->bshift, s->gpu.stream) == UG_HIP_SUCCESS &&
+                                mi355x_download_picture(dst, (size_t) s->pitch, s->dev_out.ptr, linesize, (size_t) h, s->gpu.stream) == UG_HIP_SUCCESS;
                 if (!ok) MSG(ERROR, "decode failed: %s\n", ug_hip_last_error_string());
                 return ok;
         }
@@ -239,13 +232,13 @@ static bool decode_in_bands(struct state_decompress_dxt_mi355x *s, unsigned char
         for (int k = 0; k < job.bands && ok; k++) {
                 const int r0 = job.r0[k], r1 = job.r0[k + 1];
                 const size_t off = (size_t) (r0 / 4) * block_row, end = (size_t) ((r1 + 3) / 4) * block_row;
-                char *const blocks = (char *) s->dev_in + off;
+                char *const blocks = (char *) s->dev_in.ptr + off;
                 if (off < n) { // (a short frame: the bands past its end keep what the buffer held -- the previous picture, or black)
-                        ok = ug_hip_memcpy_async(blocks, buffer + off, (end < n ? end : n) - off, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream) == UG_HIP_SUCCESS;
+                        ok = ug_hip_memcpy_async(blocks, buffer + off, (end < n ? end : n) - off, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->gpu.stream) == UG_HIP_SUCCESS;
                 }
-                ok = ok && ug_hip_dxt_decode(s->in_fmt, s->out_fmt, blocks, (char *) s->dev_out + (size_t) r0 * linesize, w, r1 - r0, 0, s->rshift, s->gshift, s->bshift,
-                                             s->stream) == UG_HIP_SUCCESS &&
-                     ug_hip_event_record(s->band_done[k], s->stream) == UG_HIP_SUCCESS;
+                ok = ok && ug_hip_dxt_decode(s->in_fmt, s->out_fmt, blocks, (char *) s->dev_out.ptr + (size_t) r0 * linesize, w, r1 - r0, 0, s->rshift, s->gshift, s->bshift,
+                                             s->gpu.stream) == UG_HIP_SUCCESS &&
+                     ug_hip_event_record(s->band_done[k], s->gpu.stream) == UG_HIP_SUCCESS;
                 if (ok) {
                         pthread_mutex_lock(&s->lock);
                         s->issued = k + 1;
@@ -273,18 +266,13 @@ static decompress_status dxt_mi355x_decompress(void *state, unsigned char *dst, 
                 MSG(ERROR, "DXT decoder not configured!\n");
                 return DECODER_NO_FRAME;
         }
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
+        if (!mi355x_gpu_enter(&s->gpu)) {
                 return DECODER_NO_FRAME;
         }
         // accepts corrupted (short) frames, property below: decode the blocks that arrived
         const size_t n = src_len < s->in_len ? src_len : s->in_len;
-        const bool ok = decode_in_bands(s, dst, buffer, n);
-        if (ug_hip_stream_sync(s->stream) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "stream sync failed: %s\n", ug_hip_last_error_string());
-                return DECODER_NO_FRAME;
-        }
-        return ok ? DECODER_GOT_FRAME : DECODER_NO_FRAME;
+        const bool ok = decode_in_bands(s, dst, buffer, n); // (says itself what failed)
+        return mi355x_gpu_finish(&s->gpu, ok, NULL) ? DECODER_GOT_FRAME : DECODER_NO_FRAME;
 }
 
 static int dxt_mi355x_decompress_get_property(void *state, int property, void *val, size_t *len)
@@ -301,7 +289,7 @@ static int dxt_mi355x_decompress_get_property(void *state, int property, void *v
 static void dxt_mi355x_decompress_done(void *state)
 {
         struct state_decompress_dxt_mi355x *s = state;
-        ug_hip_set_device(s->device);
+        mi355x_gpu_enter(&s->gpu);
         if (s->has_downloader) {
                 pthread_mutex_lock(&s->lock);
                 s->quit = true;
@@ -311,8 +299,8 @@ static void dxt_mi355x_decompress_done(void *state)
         }
         for (int k = 0; k < MI355X_MAX_BANDS; k++) ug_hip_event_destroy(s->band_done[k]);
         if (s->down) ug_hip_stream_destroy(s->down);
+        mi355x_gpu_close(&s->gpu);
         release_buffers(s);
-        if (s->stream) ug_hip_stream_destroy(s->stream);
         pthread_cond_destroy(&s->cv);
         pthread_mutex_destroy(&s->lock);
         free(s);

@@ -45,7 +45,7 @@
 #include "video_frame.h"
 #include "vo_postprocess.h"
 
-#include "mi355x_receiver.h"
+#include "mi355x_gpu_state.h"
 #include "ug_codec_map.h"
 
 #define MOD_NAME "[compose MI355X] "
@@ -62,15 +62,12 @@ struct state_cmp_mi355x {
         unsigned char  *logo;                        ///< logo: R,G,B,A on the host
         unsigned        lw, lh;
         int             x, y;
-        void           *logo_dev;
+        struct mi355x_buf logo_dev;
         struct video_desc in_desc, out_desc;         ///< crop: out_desc; all: in_desc of the last reconfigure
         struct video_frame *in[2];                   ///< the frame(s) getf hands out (interlace: odd, even)
         int             last;                        ///< interlace: 0 = odd, 1 = even (interlace.c:56-59)
-        int             device;
-        ug_hip_stream_t stream;
-        char           *host;                        ///< pinned
-        void           *dev_in[2], *dev_out;
-        size_t          host_cap, in_cap[2], out_cap;
+        struct mi355x_gpu gpu;
+        struct mi355x_buf host, dev_in[2], dev_out;  ///< host: pinned
 };
 
 static unsigned cmp_mi355x_state_count; // the states of this process take the listed devices in turn
@@ -78,30 +75,16 @@ static unsigned cmp_mi355x_state_count; // the states of this process take the l
 static void done(void *state)
 {
         struct state_cmp_mi355x *s = state;
-        if (s->stream != NULL) {
-                ug_hip_set_device(s->device);
-                ug_hip_stream_sync(s->stream);
-                if (s->host) ug_hip_free_host(s->host);
-                for (int i = 0; i < 2; i++) if (s->dev_in[i]) ug_hip_free(s->dev_in[i]);
-                if (s->dev_out) ug_hip_free(s->dev_out);
-                if (s->logo_dev) ug_hip_free(s->logo_dev);
-                ug_hip_stream_destroy(s->stream);
-        }
+        mi355x_gpu_close(&s->gpu); // (nothing on a state whose stream was never made: its bufs are empty.  The device stays the current one)
+        mi355x_buf_release(&s->host);
+        mi355x_buf_release(&s->dev_in[0]);
+        mi355x_buf_release(&s->dev_in[1]);
+        mi355x_buf_release(&s->dev_out);
+        mi355x_buf_release(&s->logo_dev);
         vf_free(s->in[0]);
         vf_free(s->in[1]);
         free(s->logo);
         free(s);
-}
-
-static bool open_device(struct state_cmp_mi355x *s)
-{
-        s->device = mi355x_next_state_device(&cmp_mi355x_state_count, MOD_NAME);
-        if (s->device < 0 || ug_hip_set_device(s->device) != UG_HIP_SUCCESS || ug_hip_stream_create(&s->stream) != UG_HIP_SUCCESS) {
-                if (s->device >= 0) MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
-                s->stream = NULL;
-                return false;
-        }
-        return true;
 }
 
 /// logo.c:72-107
@@ -149,6 +132,7 @@ static void *init_common(enum cmp_kind kind, const char *config)
                 return NULL;
         }
         s->kind = kind;
+        s->host.pinned = true;
         s->last = 1;
         s->x = s->y = -1;
         s->bw = s->bh = 10;
@@ -225,10 +209,10 @@ static void *init_common(enum cmp_kind kind, const char *config)
                 fprintf(stderr, "File name with logo required!\n");
                 ok = false;
         }
-        ok = ok && open_device(s);
+        ok = ok && mi355x_gpu_open(&s->gpu, &cmp_mi355x_state_count, MOD_NAME);
         if (ok && kind == K_LOGO) {
                 const size_t len = (size_t) 4 * s->lw * s->lh;
-                ok = ug_hip_malloc(&s->logo_dev, len) == UG_HIP_SUCCESS && ug_hip_memcpy(s->logo_dev, s->logo, len, UG_HIP_MEMCPY_HOST_TO_DEVICE) == UG_HIP_SUCCESS;
+                ok = mi355x_buf_reserve(&s->logo_dev, len) && ug_hip_memcpy(s->logo_dev.ptr, s->logo, len, UG_HIP_MEMCPY_HOST_TO_DEVICE) == UG_HIP_SUCCESS;
                 if (!ok) MSG(ERROR, "cannot upload the logo: %s\n", ug_hip_last_error_string());
         }
         if (!ok) {
@@ -331,38 +315,11 @@ static bool split_get_property(void *state, int property, void *val, size_t *len
 /// the buffers follow the frame: a pinned buffer of host_len, device inputs of in_len each, an output of out_len
 static bool reserve(struct state_cmp_mi355x *s, size_t host_len, size_t in_len, int inputs, size_t out_len)
 {
-        bool ok = true;
-        if (host_len > s->host_cap) {
-                if (s->host) ug_hip_free_host(s->host);
-                s->host = NULL, s->host_cap = 0;
-                ok = ug_hip_malloc_host((void **) &s->host, host_len) == UG_HIP_SUCCESS;
-                if (ok) s->host_cap = host_len;
-        }
-        for (int i = 0; ok && i < inputs; i++) {
-                if (in_len > s->in_cap[i]) {
-                        if (s->dev_in[i]) ug_hip_free(s->dev_in[i]);
-                        s->dev_in[i] = NULL, s->in_cap[i] = 0;
-                        ok = ug_hip_malloc(&s->dev_in[i], in_len) == UG_HIP_SUCCESS;
-                        if (ok) s->in_cap[i] = in_len;
-                }
-        }
-        if (ok && out_len > s->out_cap) {
-                if (s->dev_out) ug_hip_free(s->dev_out);
-                s->dev_out = NULL, s->out_cap = 0;
-                ok = ug_hip_malloc(&s->dev_out, out_len) == UG_HIP_SUCCESS;
-                if (ok) s->out_cap = out_len;
-        }
+        bool ok = mi355x_buf_reserve(&s->host, host_len);
+        for (int i = 0; ok && i < inputs; i++) ok = mi355x_buf_reserve(&s->dev_in[i], in_len);
+        ok = ok && mi355x_buf_reserve(&s->dev_out, out_len);
         if (!ok) MSG(ERROR, "cannot allocate the frame buffers: %s\n", ug_hip_last_error_string());
         return ok;
-}
-
-/// whatever was queued has finished when this returns, also after a failure
-static bool finish(struct state_cmp_mi355x *s, bool ok)
-{
-        if (!ok) MSG(ERROR, "%s failed: %s\n", kind_names[s->kind], ug_hip_last_error_string());
-        const bool synced = ug_hip_stream_sync(s->stream) == UG_HIP_SUCCESS;
-        if (ok && !synced) MSG(ERROR, "stream sync failed: %s\n", ug_hip_last_error_string());
-        return ok && synced;
 }
 
 static bool postprocess(void *state, struct video_frame *in, struct video_frame *out, int req_pitch)
@@ -426,21 +383,25 @@ static bool postprocess(void *state, struct video_frame *in, struct video_frame 
                 return false;
         }
         const size_t tile_len = out_pitch * rows, out_len = tile_len * out_tiles;
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS || !reserve(s, in_len * (size_t) inputs, in_len, inputs, out_len)) {
+        const struct tile *src[2] = { NULL, NULL };
+        for (int i = 0; i < inputs; i++) { // (every tile is looked at before the first copy is queued: no return below skips the synchronisation)
+                src[i] = s->kind == K_INTERLACE ? &s->in[i]->tiles[0] : &in->tiles[i];
+                if (src[i]->data_len < in_len) {
+                        MSG(ERROR, "frame shorter than %d lines of %zu bytes\n", h, L);
+                        return false;
+                }
+        }
+        if (!mi355x_gpu_enter(&s->gpu) || !reserve(s, in_len * (size_t) inputs, in_len, inputs, out_len)) {
                 return false;
         }
         bool ok = true;
         for (int i = 0; ok && i < inputs; i++) {
-                const struct tile *t = s->kind == K_INTERLACE ? &s->in[i]->tiles[0] : &in->tiles[i];
-                if (t->data_len < in_len) {
-                        MSG(ERROR, "frame shorter than %d lines of %zu bytes\n", h, L);
-                        return false;
-                }
-                memcpy(s->host + (size_t) i * in_len, t->data, in_len);
-                ok = ug_hip_upload_ordered_ex(s->device, s->dev_in[i], s->host + (size_t) i * in_len, in_len, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream, 0) == UG_HIP_SUCCESS;
+                char *const pinned = (char *) s->host.ptr + (size_t) i * in_len;
+                memcpy(pinned, src[i]->data, in_len);
+                ok = ug_hip_upload_ordered_ex(s->gpu.device, s->dev_in[i].ptr, pinned, in_len, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->gpu.stream, 0) == UG_HIP_SUCCESS;
         }
-        d.src = s->dev_in[0], d.src2 = inputs == 2 ? s->dev_in[1] : NULL, d.dst = s->dev_out;
-        ok = ok && ug_hip_compose(&d, s->stream) == UG_HIP_SUCCESS;
+        d.src = s->dev_in[0].ptr, d.src2 = inputs == 2 ? s->dev_in[1].ptr : NULL, d.dst = s->dev_out.ptr;
+        ok = ok && ug_hip_compose(&d, s->gpu.stream) == UG_HIP_SUCCESS;
         const size_t pitch = s->kind == K_SPLIT ? out_pitch : (size_t) req_pitch; // (vf_split writes its tiles packed, whatever req_pitch says)
         for (unsigned t = 0; ok && t < out_tiles; t++) {
                 if (s->kind == K_SPLIT) { // vf_split.cpp:69-76
@@ -448,14 +409,14 @@ static bool postprocess(void *state, struct video_frame *in, struct video_frame 
                         out->tiles[t].height = (unsigned) rows;
                         out->tiles[t].data_len = (unsigned) tile_len;
                 }
-                ok = pitch >= lb && ug_hip_download_2d_ordered_ex(s->device, out->tiles[t].data, pitch, (char *) s->dev_out + t * tile_len, out_pitch, lb, rows, s->stream, 0) ==
+                ok = pitch >= lb && ug_hip_download_2d_ordered_ex(s->gpu.device, out->tiles[t].data, pitch, (char *) s->dev_out.ptr + t * tile_len, out_pitch, lb, rows, s->gpu.stream, 0) ==
                                             UG_HIP_SUCCESS;
         }
         if (s->kind == K_SPLIT) {
                 out->color_spec = in->color_spec;
                 out->fps = in->fps;
         }
-        return finish(s, ok);
+        return mi355x_gpu_finish(&s->gpu, ok, kind_names[s->kind]);
 }
 
 // ---- crop as a capture filter (crop.c:200-234) ----
@@ -510,16 +471,16 @@ static struct video_frame *logo_filter(void *state, struct video_frame *in)
         }
         const size_t L = (size_t) vc_get_linesize((unsigned) w, c), len = L * s->lh;
         char *const lines = in->tiles[0].data + (size_t) ry * L;
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS || !reserve(s, len, len, 1, 0)) {
+        if (!mi355x_gpu_enter(&s->gpu) || !reserve(s, len, len, 1, 0)) {
                 return in;
         }
-        struct ug_compose_desc d = { .dst = s->dev_in[0], .op = UG_CMP_LOGO, .format = fmt, .width = w, .lines = (int) s->lh, .frames = 1, .logo = s->logo_dev,
+        struct ug_compose_desc d = { .dst = s->dev_in[0].ptr, .op = UG_CMP_LOGO, .format = fmt, .width = w, .lines = (int) s->lh, .frames = 1, .logo = s->logo_dev.ptr,
                                      .logo_w = (int) s->lw, .logo_h = (int) s->lh, .rect_x = rx, .rect_y = 0 };
-        memcpy(s->host, lines, len);
-        const bool ok = ug_hip_upload_ordered_ex(s->device, s->dev_in[0], s->host, len, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream, 0) == UG_HIP_SUCCESS &&
-                        ug_hip_compose(&d, s->stream) == UG_HIP_SUCCESS &&
-                        ug_hip_download_2d_ordered_ex(s->device, lines, L, s->dev_in[0], L, L, s->lh, s->stream, 0) == UG_HIP_SUCCESS;
-        finish(s, ok);
+        memcpy(s->host.ptr, lines, len);
+        const bool ok = ug_hip_upload_ordered_ex(s->gpu.device, s->dev_in[0].ptr, s->host.ptr, len, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->gpu.stream, 0) == UG_HIP_SUCCESS &&
+                        ug_hip_compose(&d, s->gpu.stream) == UG_HIP_SUCCESS &&
+                        ug_hip_download_2d_ordered_ex(s->gpu.device, lines, L, s->dev_in[0].ptr, L, L, s->lh, s->gpu.stream, 0) == UG_HIP_SUCCESS;
+        mi355x_gpu_finish(&s->gpu, ok, kind_names[s->kind]);
         return in;
 }
 

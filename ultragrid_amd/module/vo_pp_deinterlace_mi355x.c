@@ -40,7 +40,7 @@
 #include "video_frame.h"
 #include "vo_postprocess.h"
 
-#include "mi355x_receiver.h"
+#include "mi355x_gpu_state.h"
 #include "ug_codec_map.h"
 
 #define MOD_NAME "[deinterlace MI355X] "
@@ -52,14 +52,13 @@ struct state_deint_mi355x {
         bool                deinterlace, nodelay, force;
         bool                other_frame_emitted;
         time_ns_t           frame_received;
-        int                 device;
-        ug_hip_stream_t     stream;
+        struct mi355x_gpu   gpu;
         struct video_desc   desc;
         bool                active; ///< INTERLACED_MERGED or `force`: otherwise a copy
         bool                on_gpu; ///< the kernels take the codec
         struct video_frame *in;     ///< getf's frame; its data = host_in[cur]
-        char               *host_in[2], *stage[2]; ///< pinned: the input frames in turn (the reference's buffers[]); packed outputs
-        void               *dev_in[2], *dev_out[2];
+        struct mi355x_buf   host_in[2], stage[2]; ///< pinned: the input frames in turn (the reference's buffers[]); packed outputs
+        struct mi355x_buf   dev_in[2], dev_out[2];
         int                 cur;
         size_t              linesize, len, avg_bytes;
         int                 lines;
@@ -103,9 +102,8 @@ static void *init_common(enum deint_algo algo, const char *config)
         s->deinterlace = d;
         s->nodelay = nodelay;
         s->force = force;
-        s->device = mi355x_next_state_device(&deint_mi355x_state_count, MOD_NAME);
-        if (s->device < 0 || ug_hip_set_device(s->device) != UG_HIP_SUCCESS || ug_hip_stream_create(&s->stream) != UG_HIP_SUCCESS) {
-                if (s->device >= 0) MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
+        s->host_in[0].pinned = s->host_in[1].pinned = s->stage[0].pinned = s->stage[1].pinned = true;
+        if (!mi355x_gpu_open(&s->gpu, &deint_mi355x_state_count, MOD_NAME)) {
                 free(s);
                 return NULL;
         }
@@ -134,12 +132,10 @@ static void release(struct state_deint_mi355x *s)
                 s->in = NULL;
         }
         for (int i = 0; i < 2; i++) {
-                if (s->host_in[i]) ug_hip_free_host(s->host_in[i]);
-                if (s->stage[i]) ug_hip_free_host(s->stage[i]);
-                if (s->dev_in[i]) ug_hip_free(s->dev_in[i]);
-                if (s->dev_out[i]) ug_hip_free(s->dev_out[i]);
-                s->host_in[i] = s->stage[i] = NULL;
-                s->dev_in[i] = s->dev_out[i] = NULL;
+                mi355x_buf_release(&s->host_in[i]);
+                mi355x_buf_release(&s->stage[i]);
+                mi355x_buf_release(&s->dev_in[i]);
+                mi355x_buf_release(&s->dev_out[i]);
         }
 }
 
@@ -159,8 +155,7 @@ static size_t averaged_bytes(codec_t codec, bool linear, size_t linesize)
 static bool deint_reconfigure(void *state, struct video_desc desc)
 {
         struct state_deint_mi355x *s = state;
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
+        if (!mi355x_gpu_enter(&s->gpu)) {
                 return false;
         }
         release(s);
@@ -192,20 +187,20 @@ static bool deint_reconfigure(void *state, struct video_desc desc)
         const int n = s->algo == ALGO_BLEND ? 1 : 2;
         bool ok = (s->in = vf_alloc_desc(desc)) != NULL;
         for (int i = 0; ok && i < n; i++) {
-                ok = ug_hip_malloc_host((void **) &s->host_in[i], s->len) == UG_HIP_SUCCESS;
-                if (ok) memset(s->host_in[i], 0, s->len); // the frame "before the first": zero (the reference's is uninitialised)
+                ok = mi355x_buf_reserve(&s->host_in[i], s->len);
+                if (ok) memset(s->host_in[i].ptr, 0, s->len); // the frame "before the first": zero (the reference's is uninitialised)
                 if (ok && s->active && s->on_gpu) {
-                        ok = ug_hip_malloc_host((void **) &s->stage[i], s->len) == UG_HIP_SUCCESS && ug_hip_malloc(&s->dev_in[i], s->len) == UG_HIP_SUCCESS &&
-                             ug_hip_malloc(&s->dev_out[i], s->len) == UG_HIP_SUCCESS && ug_hip_memset_async(s->dev_in[i], 0, s->len, s->stream) == UG_HIP_SUCCESS;
+                        ok = mi355x_buf_reserve(&s->stage[i], s->len) && mi355x_buf_reserve(&s->dev_in[i], s->len) && mi355x_buf_reserve(&s->dev_out[i], s->len) &&
+                             ug_hip_memset_async(s->dev_in[i].ptr, 0, s->len, s->gpu.stream) == UG_HIP_SUCCESS;
                 }
         }
-        ok = ok && ug_hip_stream_sync(s->stream) == UG_HIP_SUCCESS;
+        ok = ok && ug_hip_stream_sync(s->gpu.stream) == UG_HIP_SUCCESS;
         if (!ok) {
                 MSG(ERROR, "cannot allocate the frame buffers: %s\n", ug_hip_last_error_string());
                 release(s);
                 return false;
         }
-        s->in->tiles[0].data = s->host_in[0];
+        s->in->tiles[0].data = s->host_in[0].ptr;
         s->in->tiles[0].data_len = (unsigned) s->len;
         return true;
 }
@@ -215,7 +210,7 @@ static struct video_frame *deint_getf(void *state)
         struct state_deint_mi355x *s = state;
         if (s->in != NULL && s->algo != ALGO_BLEND) { // the input frames in turn: the one before stays where it is (temporal-deint.c:213-221)
                 s->cur = (s->cur + 1) % 2;
-                s->in->tiles[0].data = s->host_in[s->cur];
+                s->in->tiles[0].data = s->host_in[s->cur].ptr;
         }
         return s->in;
 }
@@ -243,7 +238,7 @@ static void hand_over(const struct state_deint_mi355x *s, char *out, size_t pitc
 /// the reference's path for a codec its averages do not take, on the host: weave, bob, linear with the upper line doubled
 static void host_temporal(const struct state_deint_mi355x *s, char *out, size_t pitch, int which)
 {
-        const char *cur = s->host_in[s->cur], *prev = s->host_in[1 - s->cur];
+        const char *cur = s->host_in[s->cur].ptr, *prev = s->host_in[1 - s->cur].ptr;
         const size_t L = s->linesize;
         const int H = s->lines;
         if (s->algo == ALGO_DF) {
@@ -269,7 +264,7 @@ static bool run_gpu(struct state_deint_mi355x *s, char *out, size_t pitch)
 {
         static const int modes[] = { UG_DEINT_BLEND, UG_DEINT_WEAVE, UG_DEINT_BOB, UG_DEINT_LINEAR };
         const struct ug_deinterlace_desc d = {
-                .src = s->dev_in[s->cur], .prev = s->algo == ALGO_DF ? s->dev_in[1 - s->cur] : NULL, .dst = { s->dev_out[0], s->dev_out[1] },
+                .src = s->dev_in[s->cur].ptr, .prev = s->algo == ALGO_DF ? s->dev_in[1 - s->cur].ptr : NULL, .dst = { s->dev_out[0].ptr, s->dev_out[1].ptr },
                 .format = ug_pixfmt_from_codec(s->desc.color_spec), .mode = modes[s->algo], .blend_after_weave = s->deinterlace && s->algo == ALGO_DF,
                 .lines = s->lines, .linesize = s->linesize, .frames = 1,
         };
@@ -277,23 +272,19 @@ static bool run_gpu(struct state_deint_mi355x *s, char *out, size_t pitch)
         // BLEND: the averaged part of every line straight into `out`; LINEAR with unwritten line ends: through the packed pinned copy
         const bool staged = s->algo == ALGO_LINEAR && s->avg_bytes < L;
         const size_t width = s->algo == ALGO_BLEND && s->lines > 1 ? s->avg_bytes : L;
-        bool ok = ug_hip_upload_ordered_ex(s->device, s->dev_in[s->cur], s->host_in[s->cur], s->len, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream, 0) == UG_HIP_SUCCESS &&
-                  ug_hip_deinterlace(&d, s->stream) == UG_HIP_SUCCESS;
+        bool ok = ug_hip_upload_ordered_ex(s->gpu.device, s->dev_in[s->cur].ptr, s->host_in[s->cur].ptr, s->len, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->gpu.stream, 0) == UG_HIP_SUCCESS &&
+                  ug_hip_deinterlace(&d, s->gpu.stream) == UG_HIP_SUCCESS;
         if (ok && width > 0) {
-                ok = staged ? ug_hip_download_ordered_ex(s->device, s->stage[0], s->dev_out[0], s->len, s->stream, 0) == UG_HIP_SUCCESS
-                            : ug_hip_download_2d_ordered_ex(s->device, out, pitch, s->dev_out[0], L, width, rows, s->stream, 0) == UG_HIP_SUCCESS;
+                ok = staged ? ug_hip_download_ordered_ex(s->gpu.device, s->stage[0].ptr, s->dev_out[0].ptr, s->len, s->gpu.stream, 0) == UG_HIP_SUCCESS
+                            : ug_hip_download_2d_ordered_ex(s->gpu.device, out, pitch, s->dev_out[0].ptr, L, width, rows, s->gpu.stream, 0) == UG_HIP_SUCCESS;
         }
         if (ok && s->algo != ALGO_BLEND) {
-                ok = ug_hip_download_ordered_ex(s->device, s->stage[1], s->dev_out[1], s->len, s->stream, 0) == UG_HIP_SUCCESS;
+                ok = ug_hip_download_ordered_ex(s->gpu.device, s->stage[1].ptr, s->dev_out[1].ptr, s->len, s->gpu.stream, 0) == UG_HIP_SUCCESS;
         }
-        if (!ok) MSG(ERROR, "de-interlacing failed: %s\n", ug_hip_last_error_string());
-        // whatever was queued has finished when this returns, also after a failure (the caller reuses both frames)
-        const bool synced = ug_hip_stream_sync(s->stream) == UG_HIP_SUCCESS;
-        if (ok && !synced) MSG(ERROR, "stream sync failed: %s\n", ug_hip_last_error_string());
-        if (!ok || !synced) {
+        if (!mi355x_gpu_finish(&s->gpu, ok, "de-interlacing")) { // (the caller reuses both frames)
                 return false;
         }
-        if (staged) hand_over(s, out, pitch, s->stage[0], 0);
+        if (staged) hand_over(s, out, pitch, s->stage[0].ptr, 0);
         if (s->algo == ALGO_BLEND && s->lines > 1 && width < L) { // "the last line": the L bytes of out's line above (video_codec.c:851)
                 memcpy(out + (rows - 1) * pitch + width, out + (rows - 2) * pitch + width, L - width);
         }
@@ -328,17 +319,16 @@ static bool deint_postprocess(void *state, struct video_frame *in, struct video_
         char *o = out->tiles[0].data;
         bool ok = true;
         if (!s->active || (s->algo == ALGO_BLEND && !s->on_gpu)) {
-                copy_lines(o, pitch, s->host_in[s->cur], s->linesize, s->linesize, 0, 1, s->lines);
+                copy_lines(o, pitch, s->host_in[s->cur].ptr, s->linesize, s->linesize, 0, 1, s->lines);
         } else if (!s->on_gpu) {
                 host_temporal(s, o, pitch, in == NULL);
         } else if (in != NULL) {
-                if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS) {
-                        MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
+                if (!mi355x_gpu_enter(&s->gpu)) {
                         return false;
                 }
                 ok = run_gpu(s, o, pitch);
         } else {
-                hand_over(s, o, pitch, s->stage[1], 1);
+                hand_over(s, o, pitch, s->stage[1].ptr, 1);
         }
         if (s->algo != ALGO_BLEND && !s->nodelay) { // not both frames in bulk: wait half of the frame time (temporal-deint.c:499-510)
                 if (in != NULL) {
@@ -369,10 +359,8 @@ static void deint_get_out_desc(void *state, struct video_desc *out, int *in_disp
 static void deint_done(void *state)
 {
         struct state_deint_mi355x *s = state;
-        ug_hip_set_device(s->device);
-        if (s->stream) ug_hip_stream_sync(s->stream);
+        mi355x_gpu_close(&s->gpu); // (the device stays the current one: the buffers go after the stream has been waited for)
         release(s);
-        if (s->stream) ug_hip_stream_destroy(s->stream);
         free(s);
 }
 

@@ -30,17 +30,16 @@
 #include "video_frame.h"
 #include "vo_postprocess.h"
 
-#include "mi355x_receiver.h"
+#include "mi355x_gpu_state.h"
 
 #define MOD_NAME "[scale MI355X] "
 
 struct state_scale_mi355x {
         int                 scaled_width, scaled_height;
-        int                 device;
-        ug_hip_stream_t     stream;
+        struct mi355x_gpu   gpu;
         struct video_desc   desc;
-        struct video_frame *in; ///< getf's frame, pinned host memory
-        void               *dev_in, *dev_out;
+        struct video_frame *in; ///< getf's frame; its data = host_in
+        struct mi355x_buf   host_in, dev_in, dev_out; ///< host_in: pinned
         size_t              in_len, out_linesize;
 };
 
@@ -72,14 +71,13 @@ static bool scale_mi355x_get_property(void *state, int property, void *val, size
 static void release(struct state_scale_mi355x *s)
 {
         if (s->in) {
-                if (s->in->tiles[0].data) ug_hip_free_host(s->in->tiles[0].data);
                 s->in->tiles[0].data = NULL;
                 vf_free(s->in);
                 s->in = NULL;
         }
-        if (s->dev_in) ug_hip_free(s->dev_in);
-        if (s->dev_out) ug_hip_free(s->dev_out);
-        s->dev_in = s->dev_out = NULL;
+        mi355x_buf_release(&s->host_in);
+        mi355x_buf_release(&s->dev_in);
+        mi355x_buf_release(&s->dev_out);
 }
 
 static void *scale_mi355x_init(const char *config)
@@ -104,9 +102,8 @@ static void *scale_mi355x_init(const char *config)
         }
         s->scaled_width = w;
         s->scaled_height = h;
-        s->device = mi355x_next_state_device(&scale_mi355x_state_count, MOD_NAME);
-        if (s->device < 0 || ug_hip_set_device(s->device) != UG_HIP_SUCCESS || ug_hip_stream_create(&s->stream) != UG_HIP_SUCCESS) {
-                if (s->device >= 0) MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
+        s->host_in.pinned = true;
+        if (!mi355x_gpu_open(&s->gpu, &scale_mi355x_state_count, MOD_NAME)) {
                 free(s);
                 return NULL;
         }
@@ -116,8 +113,7 @@ static void *scale_mi355x_init(const char *config)
 static bool scale_mi355x_reconfigure(void *state, struct video_desc desc)
 {
         struct state_scale_mi355x *s = state;
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
+        if (!mi355x_gpu_enter(&s->gpu)) {
                 return false;
         }
         release(s);
@@ -142,13 +138,13 @@ static bool scale_mi355x_reconfigure(void *state, struct video_desc desc)
         s->in_len = (size_t) vc_get_linesize(desc.width, desc.color_spec) * desc.height;
         s->out_linesize = (size_t) vc_get_linesize((unsigned) s->scaled_width, desc.color_spec);
         s->in = vf_alloc_desc(desc);
-        if (s->in == NULL || ug_hip_malloc_host((void **) &s->in->tiles[0].data, s->in_len) != UG_HIP_SUCCESS ||
-            ug_hip_malloc(&s->dev_in, s->in_len) != UG_HIP_SUCCESS ||
-            ug_hip_malloc(&s->dev_out, s->out_linesize * (size_t) s->scaled_height) != UG_HIP_SUCCESS) {
+        if (s->in == NULL || !mi355x_buf_reserve(&s->host_in, s->in_len) || !mi355x_buf_reserve(&s->dev_in, s->in_len) ||
+            !mi355x_buf_reserve(&s->dev_out, s->out_linesize * (size_t) s->scaled_height)) {
                 MSG(ERROR, "cannot allocate the frame buffers: %s\n", ug_hip_last_error_string());
                 release(s);
                 return false;
         }
+        s->in->tiles[0].data = s->host_in.ptr;
         s->in->tiles[0].data_len = (unsigned) s->in_len;
         return true;
 }
@@ -172,25 +168,21 @@ static bool scale_mi355x_postprocess(void *state, struct video_frame *in, struct
                 MSG(ERROR, "pitch %d is shorter than a line of %zu bytes\n", req_pitch, s->out_linesize);
                 return false;
         }
-        if (ug_hip_set_device(s->device) != UG_HIP_SUCCESS) {
-                MSG(ERROR, "cannot use HIP device %d: %s\n", s->device, ug_hip_last_error_string());
+        if (!mi355x_gpu_enter(&s->gpu)) {
                 return false;
         }
         const struct ug_scale_desc d = {
-                .src = s->dev_in, .dst = s->dev_out, .format = s->desc.color_spec == UYVY ? UG_PF_UYVY : UG_PF_RGBA,
+                .src = s->dev_in.ptr, .dst = s->dev_out.ptr, .format = s->desc.color_spec == UYVY ? UG_PF_UYVY : UG_PF_RGBA,
                 .interlaced_merged = s->desc.interlacing == INTERLACED_MERGED,
                 .src_width = (int) s->desc.width, .src_height = (int) s->desc.height,
                 .dst_width = s->scaled_width, .dst_height = s->scaled_height, .frames = 1,
         };
-        const bool ok = ug_hip_upload_ordered_ex(s->device, s->dev_in, in->tiles[0].data, s->in_len, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->stream, 0) == UG_HIP_SUCCESS &&
-                        ug_hip_scale(&d, s->stream) == UG_HIP_SUCCESS &&
-                        ug_hip_download_2d_ordered_ex(s->device, out->tiles[0].data, (size_t) req_pitch, s->dev_out, s->out_linesize, s->out_linesize,
-                                                      (size_t) s->scaled_height, s->stream, 0) == UG_HIP_SUCCESS;
-        if (!ok) MSG(ERROR, "scale failed: %s\n", ug_hip_last_error_string());
-        // whatever was queued has finished when this returns, also after a failure (the caller reuses both frames)
-        const bool synced = ug_hip_stream_sync(s->stream) == UG_HIP_SUCCESS;
-        if (ok && !synced) MSG(ERROR, "stream sync failed: %s\n", ug_hip_last_error_string());
-        return ok && synced;
+        const bool ok = ug_hip_upload_ordered_ex(s->gpu.device, s->dev_in.ptr, in->tiles[0].data, s->in_len, UG_HIP_MEMCPY_HOST_TO_DEVICE, s->gpu.stream, 0) == UG_HIP_SUCCESS &&
+                        ug_hip_scale(&d, s->gpu.stream) == UG_HIP_SUCCESS &&
+                        ug_hip_download_2d_ordered_ex(s->gpu.device, out->tiles[0].data, (size_t) req_pitch, s->dev_out.ptr, s->out_linesize, s->out_linesize,
+                                                      (size_t) s->scaled_height, s->gpu.stream, 0) == UG_HIP_SUCCESS;
+        if (!ok) MSG(ERROR, "scale failed: %s\n", ug_hip_last_error_string()); // (said here: the bare word as a string of this object is what registering as `scale` leaves)
+        return mi355x_gpu_finish(&s->gpu, ok, NULL); // (the caller reuses both frames)
 }
 
 static void scale_mi355x_get_out_desc(void *state, struct video_desc *out, int *in_display_mode)
@@ -208,10 +200,8 @@ static void scale_mi355x_get_out_desc(void *state, struct video_desc *out, int *
 static void scale_mi355x_done(void *state)
 {
         struct state_scale_mi355x *s = state;
-        ug_hip_set_device(s->device);
-        if (s->stream) ug_hip_stream_sync(s->stream);
+        mi355x_gpu_close(&s->gpu); // (the device stays the current one: the buffers go after the stream has been waited for)
         release(s);
-        if (s->stream) ug_hip_stream_destroy(s->stream);
         free(s);
 }
 
