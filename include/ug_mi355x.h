@@ -546,7 +546,17 @@ int ug_hip_logo_geometry(ug_pixfmt_t format, int frame_w, int frame_h, int logo_
  * the colour (border.c:161-166). */
 int ug_hip_border_pattern(ug_pixfmt_t format, const unsigned char rgba[4], unsigned char out[4]);
 
-/* packed -> planar (to_planar.h:53-74) */
+/* Pitches of the planar shuffles -- the seven entry points below, ug_hip_from_planar and ug_hip_to_planar: a pitch smaller than the bytes
+ * of a line that the conversion reads or writes there is refused (UG_HIP_EINVAL, before any device call, nothing written), on either
+ * side: `width` samples for a luma, RGB or 4:4:4 plane, (width + 1) / 2 for a subsampled chroma plane (2 * that for interleaved CbCr;
+ * yuv420_to_i420: width / 2), 4 * pairs for a UYVY line (pairs = (width + 1) / 2; width / 2 where only whole pairs are written:
+ * yuv422p*_to_uyvy / yuyv), 16 * (width / 6) for yuv422p10le_to_v210's output, 16 * ceil(width / 6) for a v210 source, the tight line
+ * for the other packed outputs.  (ug_hip_to_planar walks the source of uyvy_to_nv12 by the reference's 2 * width bytes, two bytes short
+ * of a UYVY line at an odd width: by that name odd widths are refused.)
+ * Pitch 0 means "tightly packed" only where a comment says so: src_pitch of ug_hip_uyvy_to_i420 / ug_hip_v210_to_p010le and every
+ * pitch of the five decode-direction entry points; everywhere else, out_pitch of ug_hip_from_planar included (for every name alike),
+ * 0 is a short pitch. */
+/* packed -> planar (to_planar.h:53-74); src_pitch 0 = vc_get_linesize(width, UYVY), plane pitches as they are */
 int ug_hip_uyvy_to_i420(const void *src_dev, int src_pitch, void *y, int y_pitch, void *u, int u_pitch,
                         void *v, int v_pitch, int width, int height, ug_hip_stream_t stream); /* uyvy_to_i420, to_planar.c:343 */
 /* v210_to_p010le (to_planar.c:64-155) for every geometry the reference converts: any width, odd last line (:80-83), the

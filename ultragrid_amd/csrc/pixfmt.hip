@@ -10,6 +10,7 @@
 //     line-tail semantics (ragged widths, partial v210 groups, odd sizes);
 //   * fast (hot formats, aligned geometry): one lane per 16..32 input bytes, 128-bit loads,
 //     wave accesses contiguous -- these are pure HBM-bandwidth kernels.
+#include "planar_pitch.h"
 #include "ug_common.h"
 #include "rgb_yuv_device.h"
 
@@ -880,6 +881,8 @@ int ug_hip_uyvy_to_i420(const void *src, int src_pitch, void *y, int y_pitch, vo
         if (!src || !y || !u || !v || width <= 0 || height <= 0) return UG_HIP_EINVAL;
         if (!src_pitch) src_pitch = ug::linesize(UG_PF_UYVY, width);
         if (!ug::planes_ok(height, { src_pitch, y_pitch, u_pitch, v_pitch })) return ug::refuse_size("ug_hip_uyvy_to_i420");
+        const int cw = (width + 1) / 2; // (a plane pitch of 0 is a short pitch: only src_pitch has a default)
+        if (!ug::lines_fit({ src_pitch, 4LL * cw, y_pitch, width, u_pitch, cw, v_pitch, cw })) return ug::refuse_short_pitch("ug_hip_uyvy_to_i420");
         hipStream_t st = (hipStream_t) stream;
         const bool fast = width % 8 == 0 && height % 2 == 0 && !(src_pitch & 15) && !(y_pitch & 7) && !(u_pitch & 3) &&
                           !(v_pitch & 3) && !(15 & (uintptr_t) src) && !(7 & (uintptr_t) y) && !(3 & (uintptr_t) u) &&

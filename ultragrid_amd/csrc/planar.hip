@@ -12,6 +12,7 @@
 // Pure byte movement, HBM-bound: every kernel reads each input byte once and writes each output byte once.  One lane moves
 // 8 pixels (16 B of UYVY, 32 B of v210 per 12 px) with vector accesses when the geometry is aligned; ragged widths and odd
 // pitches take the per-pair path.
+#include "planar_pitch.h"
 #include "ug_common.h"
 
 namespace {
@@ -239,6 +240,7 @@ int ug_hip_yuv420p_to_uyvy(const void *y, int y_pitch, const void *cb, int cb_pi
         if (!cr_pitch) cr_pitch = cw;
         if (!dst_pitch) dst_pitch = ug::linesize(UG_PF_UYVY, width);
         if (!ug::planes_ok(height, { y_pitch, cb_pitch, cr_pitch, dst_pitch })) return ug::refuse_size("ug_hip_yuv420p_to_uyvy");
+        if (!ug::lines_fit({ y_pitch, width, cb_pitch, cw, cr_pitch, cw, dst_pitch, 4LL * cw })) return ug::refuse_short_pitch("ug_hip_yuv420p_to_uyvy");
         if (dst_pitch & 3) {
                 ug::set_last_error_msg("ug_hip_yuv420p_to_uyvy: destination pitch must be a multiple of 4");
                 return UG_HIP_EINVAL;
@@ -261,6 +263,7 @@ int ug_hip_yuv422p_to_uyvy(const void *y, int y_pitch, const void *cb, int cb_pi
         if (!cr_pitch) cr_pitch = cw;
         if (!dst_pitch) dst_pitch = ug::linesize(UG_PF_UYVY, width);
         if (!ug::planes_ok(height, { y_pitch, cb_pitch, cr_pitch, dst_pitch })) return ug::refuse_size("ug_hip_yuv422p_to_uyvy");
+        if (!ug::lines_fit({ y_pitch, width, cb_pitch, cw, cr_pitch, cw, dst_pitch, 4LL * (width / 2) })) return ug::refuse_short_pitch("ug_hip_yuv422p_to_uyvy");
         if (dst_pitch & 3) {
                 ug::set_last_error_msg("ug_hip_yuv422p_to_uyvy: destination pitch must be a multiple of 4");
                 return UG_HIP_EINVAL;
@@ -283,6 +286,9 @@ int ug_hip_yuv422p10le_to_v210(const void *y, int y_pitch, const void *cb, int c
         if (!cr_pitch) cr_pitch = 2 * cw;
         if (!dst_pitch) dst_pitch = ug::linesize(UG_PF_V210, width);
         if (!ug::planes_ok(height, { y_pitch, cb_pitch, cr_pitch, dst_pitch })) return ug::refuse_size("ug_hip_yuv422p10le_to_v210");
+        if (!ug::lines_fit({ y_pitch, 2LL * width, cb_pitch, 2LL * cw, cr_pitch, 2LL * cw, dst_pitch, 16LL * (width / 6) })) {
+                return ug::refuse_short_pitch("ug_hip_yuv422p10le_to_v210");
+        }
         if ((dst_pitch & 3) || ((y_pitch | cb_pitch | cr_pitch) & 1)) {
                 ug::set_last_error_msg("ug_hip_yuv422p10le_to_v210: pitches must keep 16-bit samples / 32-bit words aligned");
                 return UG_HIP_EINVAL;
@@ -310,6 +316,7 @@ int ug_hip_uyvy_to_i422(const void *src, int src_pitch, void *y, int y_pitch, vo
         if (!cb_pitch) cb_pitch = cw;
         if (!cr_pitch) cr_pitch = cw;
         if (!ug::planes_ok(height, { src_pitch, y_pitch, cb_pitch, cr_pitch })) return ug::refuse_size("ug_hip_uyvy_to_i422");
+        if (!ug::lines_fit({ src_pitch, 4LL * cw, y_pitch, width, cb_pitch, cw, cr_pitch, cw })) return ug::refuse_short_pitch("ug_hip_uyvy_to_i422");
         if (src_pitch & 3) {
                 ug::set_last_error_msg("ug_hip_uyvy_to_i422: source pitch must be a multiple of 4");
                 return UG_HIP_EINVAL;
@@ -343,6 +350,9 @@ int ug_hip_uyvy_to_nv12(const void *src, int src_pitch, void *y, int y_pitch, vo
         if (!y_pitch) y_pitch = width;
         if (!cbcr_pitch) cbcr_pitch = 2 * cw;
         if (!ug::planes_ok(height, { src_pitch, y_pitch, cbcr_pitch })) return ug::refuse_size("ug_hip_uyvy_to_nv12");
+        // (the reference walks its source by 2 * width, to_planar.c:213: at an odd width two bytes short of the 4 * cw a line is read for, so
+        // ug_hip_to_planar("uyvy_to_nv12") is refused here at odd widths)
+        if (!ug::lines_fit({ src_pitch, 4LL * cw, y_pitch, width, cbcr_pitch, 2LL * cw })) return ug::refuse_short_pitch("ug_hip_uyvy_to_nv12");
         if (src_pitch & 3) {
                 ug::set_last_error_msg("ug_hip_uyvy_to_nv12: source pitch must be a multiple of 4");
                 return UG_HIP_EINVAL;

@@ -21,6 +21,7 @@
 //   v210 -> P010, UYVY -> NV12, UYVY -> I420         pixfmt.hip / planar.hip entries
 #include <string.h>
 
+#include "planar_pitch.h"
 #include "ug_common.h"
 
 namespace {
@@ -501,6 +502,7 @@ int from_rgbp(const FromConv &c, const ug_from_planar_data *d, hipStream_t st)
                         ug::set_last_error_msg("ug_hip_from_planar: missing plane, or a 16-bit plane / line size at an odd address");
                         return UG_HIP_EINVAL;
                 }
+                if (!ug::lines_fit({ a.ls[i], (long long) d->width * (bytes8 ? 1 : 2) })) return ug::refuse_short_pitch("ug_hip_from_planar");
                 ptrs[i] = a.in[i];
                 ls[i] = a.ls[i];
         }
@@ -547,6 +549,10 @@ int from_yuv(const FromConv &c, const ug_from_planar_data *d, hipStream_t st)
                         ug::set_last_error_msg("ug_hip_from_planar: missing plane, or a 16-bit plane / line size at an odd address");
                         return UG_HIP_EINVAL;
                 }
+                // 4:2:2: chroma of half the width.  The bound is the plane's nominal width on purpose (include/ug_mi355x.h), not what the kernel
+                // reads: at an odd width it reads width / 2 pairs, one luma and one chroma sample less
+                const long long samples = i == 0 || c.family == FromConv::VUYA ? d->width : (d->width + 1) / 2;
+                if (!ug::lines_fit({ a.ls[i], samples * (depth > 8 ? 2 : 1) })) return ug::refuse_short_pitch("ug_hip_from_planar");
                 ptrs[i] = a.in[i];
                 ls[i] = a.ls[i];
         }
@@ -594,6 +600,9 @@ int from_i420(const ug_from_planar_data *d, hipStream_t st)
         if ((d->width | d->height) & 1) {
                 ug::set_last_error_msg("ug_hip_from_planar: yuv420_to_i420 needs even width and height");
                 return UG_HIP_EINVAL;
+        }
+        if (!ug::lines_fit({ d->in_linesize[0], d->width, d->in_linesize[1], d->width / 2, d->in_linesize[2], d->width / 2 })) {
+                return ug::refuse_short_pitch("ug_hip_from_planar");
         }
         const size_t w = (size_t) d->width, h = (size_t) d->height;
         uint8_t *dst_y = (uint8_t *) d->out_data, *dst_u = dst_y + w * h, *dst_v = dst_u + (w / 2) * (h / 2);
@@ -659,6 +668,10 @@ int ug_hip_from_planar(const char *func, const struct ug_from_planar_data *d, ug
         }
         if (d->width <= 0 || d->height <= 0 || !d->out_data) {
                 ug::set_last_error_msg("ug_hip_from_planar: bad geometry or null output");
+                return UG_HIP_EINVAL;
+        }
+        if (!d->out_pitch) { // for every name alike: the reference has no "0 = tight" (yuv420_to_i420 ignores the value, from_planar.c:371-389)
+                ug::set_last_error_msg("ug_hip_from_planar: out_pitch 0");
                 return UG_HIP_EINVAL;
         }
         hipStream_t st = (hipStream_t) stream;
@@ -735,6 +748,10 @@ int ug_hip_to_planar(const char *func, const struct ug_to_planar_data *d, ug_hip
                         ug::set_last_error_msg("ug_hip_to_planar: missing plane, or a 16-bit plane / line size at an odd address");
                         return UG_HIP_EINVAL;
                 }
+                // bytes of a line as the kernels write it: 16-bit samples, RGBA words, bytes; the P010 chroma line holds whole Cb Cr pairs
+                const long long need = c->family == ToConv::R12L ? 2LL * w : c->family == ToConv::BGRA ? 4LL * w : c->family == ToConv::I444 ? w
+                                       : i == 0 ? 2LL * w : 4LL * ((w + 1) / 2);
+                if (!ug::lines_fit({ a.ls[i], need })) return ug::refuse_short_pitch("ug_hip_to_planar");
                 optr[i] = a.out[i];
                 ols[i] = a.ls[i];
         }
