@@ -1,4 +1,4 @@
-"""GPU parity on content built for what UG_DXT_POW2_FOLD changes in encode_dxt5ycocg (dxt_encode.hip): products by powers of two inside the
+"""GPU parity on content built for the folded products of encode_dxt5ycocg (dxt_encode.hip): products by powers of two inside the
 fma of the neighbouring sum, the luma kept at 4 Y through the alpha stage.  UYVY, v210, YUV444, RGB and RGBA -> DXT5-YCoCg, both tie rules,
 512 x 32 and 510 x 30 (two waves per block row; the EDGE lane), byte for byte against the oracle, on frames built on the CPU and checked with
 the model of tests/test_dxt_pow2_fold_bound.py:
@@ -7,9 +7,7 @@ the model of tests/test_dxt_pow2_fold_bound.py:
   * luma boxes whose range after the inset lies just under and just over 2^-10, the wave test of the fast alpha stage, boxes that collapse
     (both ends clamped to one bound, from luma bytes 0-4 and 251-255) and boxes whose ends clamp at 0, at 1 and at both, spread so that some
     waves stay in the fast stage and others leave it: the fast stage, the binary search and -- where libug_mi355x_alphalinear.so is built --
-    the linear count all compare in the 4 x domain.  (The RGB front ends cannot bring a box under 2^-10: their frame holds the clamps.)
-Where libug_mi355x_nofold.so is built (make ab), the three counters of ug_hip_dxt_encode_stats_ex must be the same from it as from the product on
-every frame: which waves take which form is a property of the content."""
+    the linear count all compare in the 4 x domain.  (The RGB front ends cannot bring a box under 2^-10: their frame holds the clamps.)"""
 import ctypes as C
 import functools
 import os
@@ -165,8 +163,8 @@ def encode(so, pf, src, w, h, ties, po):
 def test_folded_encoder_on_its_seams(hip, po, size):
     from ultragrid_amd import lib as L
     w, h = size
-    product, nofold, linear = L.load(), variant("nofold"), variant("alphalinear")
-    bad, moved, left_fast = [], [], 0
+    product, linear = L.load(), variant("alphalinear")
+    bad, left_fast = [], 0
     for (name, fmt), (pf, pin, src) in sources(po, w, h).items():
         for ties, tname in ((L.TIES_EVEN, "even"), (L.TIES_AWAY, "away")):
             want = po.dxt_encode(pin, po.OUT_DXT5YCOCG, src, w, h, ties=tname)
@@ -176,17 +174,10 @@ def test_folded_encoder_on_its_seams(hip, po, size):
             if name == "luma_seams_and_clamps" and ties == L.TIES_EVEN:
                 print(f"{name} {fmt} {w}x{h}: colour full form {st[0]}, alpha full form {st[1]}, exact covariance {st[2]} waves")
                 left_fast += st[1] > 0
-            if nofold is not None:
-                got, st0 = encode(nofold, pf, src, w, h, ties, po)
-                if not np.array_equal(got, want):
-                    bad.append((name, fmt, tname, "nofold", int(np.count_nonzero(got != want))))
-                if st0 != st:
-                    moved.append((name, fmt, tname, st0, st))
             if linear is not None:
                 got, _ = encode(linear, pf, src, w, h, ties, po)
                 if not np.array_equal(got, want):
                     bad.append((name, fmt, tname, "alphalinear", int(np.count_nonzero(got != want))))
-    print(f"{w}x{h}: nofold library {'compared' if nofold is not None else 'not built'}, alphalinear library {'compared' if linear is not None else 'not built'}")
+    print(f"{w}x{h}: alphalinear library {'compared' if linear is not None else 'not built'}")
     assert not bad, bad
-    assert not moved, f"full-form / exact-covariance wave counts (nofold, product): {moved}"
     assert left_fast == 3, left_fast   # UYVY, v210 and YUV444: waves of the seam frame did leave the fast alpha stage

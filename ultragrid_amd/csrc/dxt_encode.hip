@@ -30,10 +30,6 @@
 // gives them.  Frames whose sizes ARE multiples of 4 never see any of it: their instantiation is the code it was before.
 #include "ug_common.h"
 
-#ifndef UG_DXT_TBUF
-#define UG_DXT_TBUF 1 // typed buffer loads do the byte -> float conversion (0: v_cvt_f32_ubyte in the shader; A/B switch)
-#endif
-
 namespace {
 
 constexpr float kInv255  = 0.00392156862745f;           // cuda_dxt.cu:666
@@ -94,6 +90,12 @@ __device__ __forceinline__ uint32_t palette_index(float d0, float d1, float d2, 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32_any __attribute__((aligned(1))); // a dword wherever it lies (lines of 3 * width bytes, EDGE instantiations only)
 
+#ifdef UG_FORCE_ALPHA_LINEAR // test build: the DXT5-YCoCg alpha indices always take the reference-form path (tests/test_gpu_dxt.py)
+constexpr bool kForceAlphaLinear = true;
+#else
+constexpr bool kForceAlphaLinear = false;
+#endif
+
 // acc = 2*acc + bit in ONE VALU instruction: the boolean lives in an SGPR lane mask (it is the
 // result of v_cmp / SALU mask logic) and is consumed as the carry-in of v_addc_co_u32.
 typedef unsigned long long lanemask_t;
@@ -105,6 +107,14 @@ __device__ __forceinline__ uint32_t shift_in(uint32_t acc, lanemask_t mask)
         uint32_t r;
         asm("v_addc_co_u32_e64 %0, %1, %2, %2, %3" : "=v"(r), "=s"(carry_out) : "v"(acc), "s"(mask));
         return r;
+}
+// the full forms of both encoders: the two index bits of one pixel (glsl:237-244, as palette_index) shifted into w on the lane masks
+__device__ __forceinline__ uint32_t shift_in_palette_index(uint32_t w, float d0, float d1, float d2, float d3)
+{
+        const lanemask_t b0 = LANEMASK(d0 > d3), b1 = LANEMASK(d1 > d2), b2 = LANEMASK(d0 > d2),
+                         b3 = LANEMASK(d1 > d3), b4 = LANEMASK(d2 > d3);
+        w = shift_in(w, (b1 & b2) | (b0 & b3)); // bit 2i+1
+        return shift_in(w, b0 & b4);            // bit 2i
 }
 
 // acc + carry (v_addc with a zero addend): adds the boolean of a lane mask to a count
@@ -132,54 +142,15 @@ __device__ __forceinline__ uint32_t spread16(uint32_t x)
         return x;
 }
 
-// Per-wave LDS tables of the fast index stages (UG_DXT_FAST_INDEX): every lane owns one column, nothing is shared
+// Per-wave LDS tables of the fast index stages: every lane owns one column, nothing is shared
 // between lanes, so no barrier is involved.  Row-major by entry: a wave's access to one row is 64 consecutive words / 16-byte units.
-#ifndef UG_DXT_NO_FAST_INDEX
-#define UG_DXT_FAST_INDEX 1
-#else
-#define UG_DXT_FAST_INDEX 0
-#endif
 // pixels per group of the fast stages' software pipelines (table reads of group n + 1 in flight while group n is evaluated).
 // Measured, interleaved A/B on UYVY->DXT5 4K: colour groups of 2 / 4 and luma groups of 4 / 8 are equal within 0.3 %; 8 / 16 spill.
-#ifndef UG_DXT1_FAST_GROUP
-#define UG_DXT1_FAST_GROUP 2
-#endif
-#ifndef UG_DXT5_FAST_GROUP
-#define UG_DXT5_FAST_GROUP 4
-#endif
-#ifndef UG_DXT5_ALPHA_GROUP
-#define UG_DXT5_ALPHA_GROUP 8
-#endif
-// DXT5-YCoCg colour stage: 4:2:2 sources hold ONE chroma sample per horizontal pixel pair, so the pair is located on the palette
-// segment once, from its even pixel (1 = on; 0 = every pixel located on its own; A/B switch).  Only loaders with kChromaPairs take it.
-#ifndef UG_DXT_PAIR_ZONE
-#define UG_DXT_PAIR_ZONE 1
-#endif
+constexpr int kDxt1FastGroup = 2, kDxt5FastGroup = 4, kDxt5AlphaGroup = 8;
 // DXT5-YCoCg fast stages: the row of the lookup table is read from the mantissa of fma(u, rows - 1, 2^23) instead of
-// v_cvt_u32_f32(u * rows) (1 = on; A/B switch).  kIndexBias + n, n = 0 .. 7, is the integer 2^23 + n: one ulp = 1 in that binade.
-#ifndef UG_DXT_BITS_INDEX
-#define UG_DXT_BITS_INDEX 1
-#endif
-// DXT5-YCoCg diagonal (SelectYCoCgDiagonal): with one chroma sample per pixel pair the SIGN of the covariance is taken from one product
-// per pair under an error certificate; a wave with an uncertified block forms the reference's 16-term sum (1 = on; 0 = the
-// reference's sum for every block; A/B switch).  Only loaders with kChromaPairs take it.
-#ifndef UG_DXT_PAIR_COV
-#define UG_DXT_PAIR_COV 1
-#endif
-// DXT5-YCoCg: products by a power of two, which are exact in binary32, ride inside the fma of the neighbouring sum, and the luma is kept
-// at 4 Y = r + 2 g + b through the alpha stage (1 = on; 0 = one instruction per product as the reference writes them; A/B switch).  The
-// argument is in encode_dxt5ycocg.
-#ifndef UG_DXT_POW2_FOLD
-#define UG_DXT_POW2_FOLD 1
-#endif
-// DXT5-YCoCg colour stage: with one chroma sample per pixel pair the open comparison da > db is the sign of a linear form of the pixel,
-// taken ONCE per pair from two fma under an error certificate; a wave with an uncertified block evaluates the reference's two squared
-// distances for every pixel (1 = on; 0 = the distances for every pixel; A/B switch).  Only where the pair location (UG_DXT_PAIR_ZONE) is.
-#ifndef UG_DXT_PAIR_LINEAR
-#define UG_DXT_PAIR_LINEAR 1
-#endif
-[[maybe_unused]] constexpr float kIndexBias = 8388608.0f;      // 2^23
-[[maybe_unused]] constexpr uint32_t kIndexBits = 0x4b000000u;  // its bits: lowest set bit 24, so kIndexBits << 8 == 0 (mod 2^32) -- a row offset needs no correction
+// v_cvt_u32_f32(u * rows).  kIndexBias + n, n = 0 .. 7, is the integer 2^23 + n: one ulp = 1 in that binade.
+constexpr float kIndexBias = 8388608.0f;      // 2^23
+constexpr uint32_t kIndexBits = 0x4b000000u;  // its bits: lowest set bit 24, so kIndexBits << 8 == 0 (mod 2^32) -- a row offset needs no correction
 // what `fields` accumulations acc = (acc << shift) + (kIndexBits + n) leave in a 32-bit word besides the n (wrap-around arithmetic)
 constexpr uint32_t index_bias_sum(int fields, int shift)
 {
@@ -204,7 +175,7 @@ __device__ __forceinline__ void count_exact_cov()
                 atomicAdd(&g_exact_cov_waves, 1ull);
         }
 }
-// and for the colour stage's linear form (UG_DXT_PAIR_LINEAR): waves that went on to the per-pixel distances.  That side is no rare
+// and for the colour stage's linear form: waves that went on to the per-pixel distances.  That side is no rare
 // path -- a few percent of the waves of ordinary video take it, all of them on content built for it -- and atomics on ONE address are served
 // one after the other: 129 600 counting waves per launch cost 1.4 ms beside 0.14 ms of encoding.  So the count is kept in kPairSlots
 // slots, each in a 128-byte line of its own, chosen by workgroup and wave; ug_hip_dxt_encode_stats_ex adds them up.
@@ -355,128 +326,7 @@ struct LoaderRGBAWords {
 };
 
 // ---- UYVY: 8 B per block row; chroma replicated (yuv422_to_yuv444.glsl:22-30) ----
-template <bool CONVERT>
-struct LoaderUYVY {
-        static constexpr int kBlocks = 1;
-        static constexpr bool kChromaPairs = CONVERT; // pixels 2j, 2j + 1 of a row come out of one yuv_pair_to_rgb call (raw Y,Cb,Cr in the RGB channels: the pair shares g and b only, not Co / Cg)
-        uint2 w[4];
-        template <bool EDGE = false>
-        __device__ __forceinline__ void load(const uint8_t *src, uint32_t pitch, uint32_t unit_x, const int (&rows)[4])
-        {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                        if (EDGE) { // 2 * width bytes per line, width even: 4-byte alignment
-                                const uint32_t *q = (const uint32_t *) (src + ((uint32_t) rows[r] * pitch + unit_x * 8u));
-                                w[r] = make_uint2(q[0], q[1]);
-                        } else {
-                                w[r] = *(const uint2 *) (src + ((uint32_t) rows[r] * pitch + unit_x * 8u));
-                        }
-                }
-        }
-        // width = 2 (mod 4): one U Y0 V Y1 group exists; the second one repeats its last pixel: U Y1 V Y1
-        __device__ __forceinline__ void load_edge(const uint8_t *src, uint32_t pitch, uint32_t unit_x, const int (&rows)[4], int)
-        {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                        const uint32_t q = *(const uint32_t *) (src + ((uint32_t) rows[r] * pitch + unit_x * 8u));
-                        w[r] = make_uint2(q, (q & 0xffff00ffu) | (q >> 24) << 8);
-                }
-        }
-        __device__ __forceinline__ void block(int, Px16 &p) const
-        {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                        const uint32_t q[2] = { w[r].x, w[r].y };
-#pragma unroll
-                        for (int k = 0; k < 2; k++) {
-                                const float u = byte_f(q[k], 0), y0 = byte_f(q[k], 1);
-                                const float v = byte_f(q[k], 2), y1 = byte_f(q[k], 3);
-                                const int i = 4 * r + 2 * k;
-                                if (CONVERT) {
-                                        yuv_pair_to_rgb(y0, y1, u, v, p, i);
-                                } else { // DXT1_YUV: YCbCr stored in the RGB channels (dxt_encoder.c:318-323)
-                                        p.a[i] = y0; p.b[i] = u; p.c[i] = v;
-                                        p.a[i + 1] = y1; p.b[i + 1] = u; p.c[i + 1] = v;
-                                }
-                        }
-                }
-        }
-};
-#ifndef UG_DXT_LDS_CONV
-#define UG_DXT_LDS_CONV 0 // experiment of round 4: 1 = the byte -> term maps of ConvertYUVToRGB are 256-entry tables in LDS
-#endif
-#if UG_DXT_LDS_CONV
-// Every term of ConvertYUVToRGB is a function of ONE byte: Y' = 1.1643 * (y / 255 - 0.0625), (1.7926, 0.5328) * (v / 255 - 0.5),
-// (0.2132, 2.1124) * (u / 255 - 0.5).  The workgroup builds the three tables once, with the very statements of yuv_pair_to_rgb -- the entries
-// are bit-identical by construction --, and a pixel pair then costs 4 table reads (the LDS pipe is idle in this kernel) + the 8 additions
-// instead of 22 VALU operations.  Raw word loads; the byte -> table offset is one shift with a byte selector.
-struct ConvTables {
-        float y[256];
-        float2 v[256]; // (rv, gv)
-        float2 u[256]; // (gu, bu)
-};
-template <bool CONVERT>
-struct LoaderUYVYLds {
-        static constexpr int kBlocks = 1;
-        static constexpr bool kChromaPairs = CONVERT; // pixels 2j, 2j + 1 of a row come out of one yuv_pair_to_rgb call (raw Y,Cb,Cr in the RGB channels: the pair shares g and b only, not Co / Cg)
-        static constexpr bool kLdsConv = CONVERT;
-        uint2 w[4];
-        const ConvTables *lut;
-        template <bool EDGE = false>
-        __device__ __forceinline__ void load(const uint8_t *src, uint32_t pitch, uint32_t unit_x, const int (&rows)[4])
-        {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                        if (EDGE) { // 2 * width bytes per line, width even: 4-byte alignment
-                                const uint32_t *q = (const uint32_t *) (src + ((uint32_t) rows[r] * pitch + unit_x * 8u));
-                                w[r] = make_uint2(q[0], q[1]);
-                        } else {
-                                w[r] = *(const uint2 *) (src + ((uint32_t) rows[r] * pitch + unit_x * 8u));
-                        }
-                }
-        }
-        // width = 2 (mod 4): one U Y0 V Y1 group exists; the second one repeats its last pixel: U Y1 V Y1
-        __device__ __forceinline__ void load_edge(const uint8_t *src, uint32_t pitch, uint32_t unit_x, const int (&rows)[4], int)
-        {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                        const uint32_t q = *(const uint32_t *) (src + ((uint32_t) rows[r] * pitch + unit_x * 8u));
-                        w[r] = make_uint2(q, (q & 0xffff00ffu) | (q >> 24) << 8);
-                }
-        }
-        __device__ __forceinline__ void block(int, Px16 &p) const
-        {
-                const char *const ty = (const char *) lut->y, *const tv = (const char *) lut->v, *const tu = (const char *) lut->u;
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                        const uint32_t q[2] = { w[r].x, w[r].y };
-#pragma unroll
-                        for (int k = 0; k < 2; k++) {
-                                const int i = 4 * r + 2 * k;
-                                if (CONVERT) {
-                                        const uint32_t ou = (q[k] & 0xffu) << 3, oy0 = ((q[k] >> 8) & 0xffu) << 2;
-                                        const uint32_t ov = ((q[k] >> 16) & 0xffu) << 3, oy1 = (q[k] >> 24) << 2;
-                                        const float2 gb = *(const float2 *) (tu + ou), rg = *(const float2 *) (tv + ov);
-                                        const float Y0 = *(const float *) (ty + oy0), Y1 = *(const float *) (ty + oy1);
-                                        p.a[i] = Y0 + rg.x;
-                                        p.b[i] = (Y0 - gb.x) - rg.y;
-                                        p.c[i] = Y0 + gb.y;
-                                        p.a[i + 1] = Y1 + rg.x;
-                                        p.b[i + 1] = (Y1 - gb.x) - rg.y;
-                                        p.c[i + 1] = Y1 + gb.y;
-                                } else {
-                                        const float u = byte_f(q[k], 0), y0 = byte_f(q[k], 1), v = byte_f(q[k], 2), y1 = byte_f(q[k], 3);
-                                        p.a[i] = y0; p.b[i] = u; p.c[i] = v;
-                                        p.a[i + 1] = y1; p.b[i + 1] = u; p.c[i + 1] = v;
-                                }
-                        }
-                }
-        }
-};
-template <> struct Loader<UG_PF_UYVY> : LoaderUYVYLds<true> {};
-template <> struct Loader<UG_PF_UYVY_RAW> : LoaderUYVYLds<false> {};
-#elif UG_DXT_TBUF
-// Same, but the texture-address unit does the byte -> float conversion: typed buffer loads with format 8_8_8_8 USCALED return
+// The texture-address unit does the byte -> float conversion: typed buffer loads with format 8_8_8_8 USCALED return
 // float(byte) for the four bytes of a word (exact), so the 32 v_cvt_f32_ubyte of a block -- slow-pipe VALU work -- disappear; the
 // multiplication by kInv255 stays in the shader arithmetic.  Costs 24 more VGPRs (the raw block is held as 32 floats).
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -531,7 +381,7 @@ struct LoaderUYVYTyped {
                                 const int i = 4 * r + 2 * k;
                                 if (CONVERT) {
                                         yuv_pair_to_rgb(y0, y1, u, v, p, i);
-                                } else {
+                                } else { // DXT1_YUV: YCbCr stored in the RGB channels (dxt_encoder.c:318-323)
                                         p.a[i] = y0; p.b[i] = u; p.c[i] = v;
                                         p.a[i + 1] = y1; p.b[i + 1] = u; p.c[i + 1] = v;
                                 }
@@ -541,11 +391,6 @@ struct LoaderUYVYTyped {
 };
 template <> struct Loader<UG_PF_UYVY> : LoaderUYVYTyped<true> {};
 template <> struct Loader<UG_PF_UYVY_RAW> : LoaderUYVYTyped<false> {};
-
-#else
-template <> struct Loader<UG_PF_UYVY> : LoaderUYVY<true> {};
-template <> struct Loader<UG_PF_UYVY_RAW> : LoaderUYVY<false> {};
-#endif
 // RGB / YUV444 / RGBA keep word loads: measured with typed loads RGBA is equal and RGB (three 4-byte typed loads per 12-byte row) twice
 // as slow -- the address unit, not the VALU, becomes the limit.
 template <> struct Loader<UG_PF_RGB> : Loader3<false> {};
@@ -605,62 +450,72 @@ struct Loader<UG_PF_V210> {
 // ---------------------------------------------------------------------------------------
 // DXT5-YCoCg block encode (compress_dxt5ycocg_fp.glsl:326-377 / cuda_dxt.cu:471-509)
 // ---------------------------------------------------------------------------------------
-// PAIRS: pixels 2j, 2j + 1 of a row share their chroma sample (Loader::kChromaPairs)
-template <bool AWAY, bool PAIRS>
-__device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &tab)
+// The stages that stand alone are functions named after the shader's routines; the others follow in encode_dxt5ycocg, in the shader's order.
+// PAIRS (select_ycocg_diagonal, encode_dxt5ycocg): pixels 2j, 2j + 1 of a row share their chroma sample (Loader::kChromaPairs).
+//
+// Exact products by powers of two, for every stage below:
+// ConvertRGBToYCoCg (glsl:27-34).  2.0*x and *0.25 are exact (powers of two), so
+//   (r + 2g + b)*0.25      : fma(g,2,r) == r + 2g bit-for-bit (2g exact)
+//   (2r - 2b)*0.25 + off   : 2r-2b == 2(r-b) exactly, *0.25 exact -> (r-b)*0.5 + off,
+//                            and fma(r-b, 0.5, off) == ((r-b)*0.5) + off (product exact)
+//   (-r + 2g - b)*0.25+off : fma(g,2,-r) == -r + 2g ; fma(t,0.25,off) == t*0.25 + off
+//
+// The same rule through the rest of encode_dxt5ycocg.  x * 2^k is exact unless it underflows, so
+// RN(x * 2^k + c) == fma(x, 2^k, c) and RN(2^k x) == 2^k RN(x): wherever the reference multiplies by 2, 4, 8, 16, 1/2, 1/4, 1/16 or
+// 1/32 and adds, the product moves into the fma of the sum, and the luma is never scaled at all: Y4 = r + 2 g + b = 4 Y is kept, and
+// what it feeds is homogeneous of degree 1 (fmin / fmax commute with the scale, +, - and * by a constant scale with it), so the
+// alpha stage compares Y4 <= 4 T where the reference compares Y <= T.  Sites, with the smallest non-zero magnitude the scaled
+// operand takes (tests/test_dxt_pow2_fold_bound.py enumerates the first, and restates every site in strict fp32):
+//   Y4 = t + b       the deleted * 0.25.  RGB front ends: r, g, b are bytes / 255, a non-zero r + 2 g + b is >= 1 / 255.  YUV front
+//                    ends: r, g, b are sums of 1.1643 (y - 1/16) and products of (u | v) - 1/2 by constants of 0.2 .. 2.1, y, u, v
+//                    bytes / 255.  y - 1/16 and u - 1/2 are 0 or multiples of the byte's last place, >= 2^-31 (a byte / 255 is
+//                    >= 2^-8), and at least 2^-12 (|16 / 255 - 1/16|, |127.5 - 127| / 255) in magnitude, so every term is 0 or >= 2^-15
+//                    with its last place >= 2^-39, and so is the last place of any sum of them: a non-zero t + b is >= 2^-39.
+//                    The enumeration of every (y, u, v) finds 3 * 2^-28 at the least.
+//   box ends         mnY + inset = fma(mn4, 1/4, inset) and inset = fma(mx4 - mn4, 1/128, -kInsetY): mx4 - mn4 = 4 (mxY - mnY)
+//                    exactly, and / 128 of it is the reference's / 32.  The two ends leave the 4 x domain here, BEFORE the clamp
+//                    and the * 255 rounding, through the fma they needed anyway (clamp modifier as before: no v_med3 to [0, 4],
+//                    no 63.75, no instruction more than the reference's own inset: chosen over clamping in the 4 x domain, which
+//                    costs two v_med3, at equal registers).  The thresholds go back up through their CONSTANTS: see there.
+//   chroma ends      fma(mx - off, fs, off), fs = 1, 2, 4; insets fma(a - b, 1/16, -kInsetC); dequantised ends
+//                    fma(x / 255 - off, rfs, off), rfs = 1, 1/2, 1/4.  Co, Cg and the end points are floats in (-2, 3) built from the
+//                    terms above and off = 128 / 255, so multiples of 2^-39 again; mx - off, a - b and x / 255 - off are differences
+//                    of two of them, or of one and a constant of that kind: equal, or >= 2^-39 apart (>= 2^-25 where both are near 1/2).
+//   thresholds       (8 - k) mx + (k - 1) mn with one multiplier a power of two: that product inside the fma.
+// No operand comes anywhere near 2^-124, below which a product by 1/32 would be denormal.  Overflow is out of the question
+// (|values| < 16).  The reference writes one operation per product: (t + b) * 0.25 here, and so on at every site.
+
+// ConvertRGBToYCoCg (glsl:27-34, the first lines of the block comment above): (r, g, b) in p.a / p.b / p.c -> (4 Y, Co, Cg) in place
+__device__ __forceinline__ void convert_rgb_to_ycocg(Px16 &p)
 {
-        // ConvertRGBToYCoCg (glsl:27-34).  2.0*x and *0.25 are exact (powers of two), so
-        //   (r + 2g + b)*0.25      : fma(g,2,r) == r + 2g bit-for-bit (2g exact)
-        //   (2r - 2b)*0.25 + off   : 2r-2b == 2(r-b) exactly, *0.25 exact -> (r-b)*0.5 + off,
-        //                            and fma(r-b, 0.5, off) == ((r-b)*0.5) + off (product exact)
-        //   (-r + 2g - b)*0.25+off : fma(g,2,-r) == -r + 2g ; fma(t,0.25,off) == t*0.25 + off
-        //
-        // The same rule through the rest of the function (UG_DXT_POW2_FOLD).  x * 2^k is exact unless it underflows, so
-        // RN(x * 2^k + c) == fma(x, 2^k, c) and RN(2^k x) == 2^k RN(x): wherever the reference multiplies by 2, 4, 8, 16, 1/2, 1/4, 1/16 or
-        // 1/32 and adds, the product moves into the fma of the sum, and the luma is never scaled at all: Y4 = r + 2 g + b = 4 Y is kept, and
-        // what it feeds is homogeneous of degree 1 (fmin / fmax commute with the scale, +, - and * by a constant scale with it), so the
-        // alpha stage compares Y4 <= 4 T where the reference compares Y <= T.  Sites, with the smallest non-zero magnitude the scaled
-        // operand takes (tests/test_dxt_pow2_fold_bound.py enumerates the first, and restates every site in strict fp32):
-        //   Y4 = t + b       the deleted * 0.25.  RGB front ends: r, g, b are bytes / 255, a non-zero r + 2 g + b is >= 1 / 255.  YUV front
-        //                    ends: r, g, b are sums of 1.1643 (y - 1/16) and products of (u | v) - 1/2 by constants of 0.2 .. 2.1, y, u, v
-        //                    bytes / 255.  y - 1/16 and u - 1/2 are 0 or multiples of the byte's last place, >= 2^-31 (a byte / 255 is
-        //                    >= 2^-8), and at least 2^-12 (|16 / 255 - 1/16|, |127.5 - 127| / 255) in magnitude, so every term is 0 or >= 2^-15
-        //                    with its last place >= 2^-39, and so is the last place of any sum of them: a non-zero t + b is >= 2^-39.
-        //                    The enumeration of every (y, u, v) finds 3 * 2^-28 at the least.
-        //   box ends         mnY + inset = fma(mn4, 1/4, inset) and inset = fma(mx4 - mn4, 1/128, -kInsetY): mx4 - mn4 = 4 (mxY - mnY)
-        //                    exactly, and / 128 of it is the reference's / 32.  The two ends leave the 4 x domain here, BEFORE the clamp
-        //                    and the * 255 rounding, through the fma they needed anyway (clamp modifier as before: no v_med3 to [0, 4],
-        //                    no 63.75, no instruction more than the reference's own inset: chosen over clamping in the 4 x domain, which
-        //                    costs two v_med3, at equal registers).  The thresholds go back up through their CONSTANTS: see there.
-        //   chroma ends      fma(mx - off, fs, off), fs = 1, 2, 4; insets fma(a - b, 1/16, -kInsetC); dequantised ends
-        //                    fma(x / 255 - off, rfs, off), rfs = 1, 1/2, 1/4.  Co, Cg and the end points are floats in (-2, 3) built from the
-        //                    terms above and off = 128 / 255, so multiples of 2^-39 again; mx - off, a - b and x / 255 - off are differences
-        //                    of two of them, or of one and a constant of that kind: equal, or >= 2^-39 apart (>= 2^-25 where both are near 1/2).
-        //   thresholds       (8 - k) mx + (k - 1) mn with one multiplier a power of two: that product inside the fma.
-        // No operand comes anywhere near 2^-124, below which a product by 1/32 would be denormal.  Overflow is out of the question
-        // (|values| < 16).  With -DUG_DXT_POW2_FOLD=0 every statement is the parent's.
-        constexpr bool kFold = UG_DXT_POW2_FOLD;
 #pragma unroll
         for (int i = 0; i < 16; i++) {
                 const float r = p.a[i], g = p.b[i], b = p.c[i];
                 const float t = __builtin_fmaf(g, 2.0f, r);
-                p.a[i] = kFold ? t + b : (t + b) * 0.25f; // kFold: Y4 = 4 Y
+                p.a[i] = t + b; // Y4 = 4 Y
                 p.b[i] = __builtin_fmaf(r - b, 0.5f, kOffset);
                 p.c[i] = __builtin_fmaf(__builtin_fmaf(g, 2.0f, -r) - b, 0.25f, kOffset);
         }
-        float *Y = p.a, *Co = p.b, *Cg = p.c; // kFold: Y[] holds Y4, and so do mnY / mxY up to InsetYBBox
+}
 
-        // FindMinMaxColorsBox (glsl:69-78)
-        float mnY = Y[0], mxY = Y[0], mnCo = Co[0], mxCo = Co[0], mnCg = Cg[0], mxCg = Cg[0];
+// FindMinMaxColorsBox (glsl:69-78).  Y[] holds Y4, and so do mnY / mxY
+__device__ __forceinline__ void find_min_max_colors_box(const float *Y, const float *Co, const float *Cg, float &mnY, float &mxY, float &mnCo,
+                                                        float &mxCo, float &mnCg, float &mxCg)
+{
+        mnY = Y[0]; mxY = Y[0]; mnCo = Co[0]; mxCo = Co[0]; mnCg = Cg[0]; mxCg = Cg[0];
 #pragma unroll
         for (int i = 1; i < 16; i++) {
                 mnY = fminf(mnY, Y[i]);    mxY = fmaxf(mxY, Y[i]);
                 mnCo = fminf(mnCo, Co[i]); mxCo = fmaxf(mxCo, Co[i]);
                 mnCg = fminf(mnCg, Cg[i]); mxCg = fmaxf(mxCg, Cg[i]);
         }
+}
 
-        // SelectYCoCgDiagonal (glsl:169-183): sequential sum, i = 0..15
-        if constexpr (!(PAIRS && UG_DXT_PAIR_COV)) {
+// SelectYCoCgDiagonal (glsl:169-183): sequential sum, i = 0..15.  True where the covariance is negative: the caller swaps the Cg ends.
+template <bool PAIRS>
+__device__ __forceinline__ bool select_ycocg_diagonal(const float *Co, const float *Cg, float mnCo, float mxCo, float mnCg, float mxCg)
+{
+        if constexpr (!PAIRS) {
                 const float midx = (mxCo + mnCo) * 0.5f, midy = (mxCg + mnCg) * 0.5f;
                 float cov = 0.0f;
 #pragma unroll
@@ -668,11 +523,9 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         const float tx = Co[i] - midx, ty = Cg[i] - midy;
                         cov = cov + tx * ty;
                 }
-                if (cov < 0.0f) {
-                        const float t = mxCg; mxCg = mnCg; mnCg = t;
-                }
+                return cov < 0.0f;
         } else {
-                // One product per chroma pair (PAIRS, UG_DXT_PAIR_COV).  The reference uses cov for its SIGN only, so the sign is found
+                // One product per chroma pair (PAIRS).  The reference uses cov for its SIGN only, so the sign is found
                 // from a cheaper sum and the reference's own sum is kept for the blocks where that one cannot tell.
                 //   rough = sum over the 8 EVEN pixels of tx ty, accumulated with fma: half of cov, up to the errors below.
                 // With hx = mxCo - mnCo, hy = mxCg - mnCg every |tx| <= hx / 2, |ty| <= hy / 2 (+ half an ulp of mid's own rounding, < 6e-8,
@@ -718,9 +571,50 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         }
                         swap = cov < 0.0f;
                 }
-                if (swap) {
-                        const float t = mxCg; mxCg = mnCg; mnCg = t;
+                return swap;
+        }
+}
+
+// The reference's form of EmitIndicesYCoCgDXT5 (glsl:217-250), for the waves the fast stage in encode_dxt5ycocg does not take.  The four squared
+// distances of TWO horizontally adjacent pixels are computed with packed fp32 (v_pk_add/v_pk_mul: IEEE per component, so
+// bit-identical to the scalar form).
+__device__ __forceinline__ uint32_t emit_indices_ycocg_full_form(const float *Co, const float *Cg, const float (&cx)[4], const float (&cy)[4])
+{
+        uint32_t w_cidx = 0;
+        f32x2 cx2[4], cy2[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+                cx2[k] = (f32x2) { cx[k], cx[k] };
+                cy2[k] = (f32x2) { cy[k], cy[k] };
+        }
+#pragma unroll
+        for (int i = 14; i >= 0; i -= 2) { // pixel pairs, last first: bits are shifted in MSB first
+                const f32x2 co = { Co[i], Co[i + 1] }, cg = { Cg[i], Cg[i + 1] };
+                f32x2 d[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                        const f32x2 tx = co - cx2[k], ty = cg - cy2[k];
+                        d[k] = tx * tx + ty * ty;
                 }
+#pragma unroll
+                for (int h = 1; h >= 0; h--) { // pixel i+1, then pixel i
+                        w_cidx = shift_in_palette_index(w_cidx, d[0][h], d[1][h], d[2][h], d[3][h]);
+                }
+        }
+        return w_cidx;
+}
+
+template <bool AWAY, bool PAIRS>
+__device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &tab)
+{
+        convert_rgb_to_ycocg(p);
+        const float *Y = p.a, *Co = p.b, *Cg = p.c; // Y[] holds Y4, and so do mnY / mxY up to InsetYBBox
+
+        float mnY, mxY, mnCo, mxCo, mnCg, mxCg;
+        find_min_max_colors_box(Y, Co, Cg, mnY, mxY, mnCo, mxCo, mnCg, mxCg);
+
+        if (select_ycocg_diagonal<PAIRS>(Co, Cg, mnCo, mxCo, mnCg, mxCg)) {
+                const float t = mxCg; mxCg = mnCg; mnCg = t;
         }
 
         // ScaleYCoCg (glsl:150-167)
@@ -734,7 +628,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 if (m < (float) (32.0 / 255.0)) { scale = 4; fs = 4.0f; rfs = 0.25f; }
         }
 
-        // EmitEndPointsYCoCgDXT5 (glsl:185-215) with InsetCoCgBBox (glsl:92-97).
+        // EmitEndPointsYCoCgDXT5 (glsl:185-215) with InsetCoCgBBox (glsl:92-97).  cmx / cmn: the dequantised ends the palette is built from.
         // "/ 16.0" and "/ float(scale)" are multiplications by exact powers of two.
         uint32_t w_end;
         float cmx[2], cmn[2];
@@ -744,9 +638,9 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 uint32_t imax[2], imin[2];
 #pragma unroll
                 for (int k = 0; k < 2; k++) {
-                        float a = kFold ? __builtin_fmaf(mx_in[k] - kOffset, fs, kOffset) : (mx_in[k] - kOffset) * fs + kOffset;
-                        float b = kFold ? __builtin_fmaf(mn_in[k] - kOffset, fs, kOffset) : (mn_in[k] - kOffset) * fs + kOffset;
-                        const float inset = kFold ? __builtin_fmaf(a - b, 0.0625f, -kInsetC) : (a - b) * 0.0625f - kInsetC;
+                        float a = __builtin_fmaf(mx_in[k] - kOffset, fs, kOffset);
+                        float b = __builtin_fmaf(mn_in[k] - kOffset, fs, kOffset);
+                        const float inset = __builtin_fmaf(a - b, 0.0625f, -kInsetC);
                         b = clamp01(b + inset);
                         a = clamp01(a - inset);
                         imax[k] = round_u32<AWAY>(a * q[k]);
@@ -761,21 +655,15 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 const float inv255 = (float) (1.0 / 255.0);
 #pragma unroll
                 for (int k = 0; k < 2; k++) {
-                        cmx[k] = kFold ? __builtin_fmaf((float) imax[k] * inv255 - kOffset, rfs, kOffset) : ((float) imax[k] * inv255 - kOffset) * rfs + kOffset;
-                        cmn[k] = kFold ? __builtin_fmaf((float) imin[k] * inv255 - kOffset, rfs, kOffset) : ((float) imin[k] * inv255 - kOffset) * rfs + kOffset;
+                        cmx[k] = __builtin_fmaf((float) imax[k] * inv255 - kOffset, rfs, kOffset);
+                        cmn[k] = __builtin_fmaf((float) imin[k] * inv255 - kOffset, rfs, kOffset);
                 }
         }
 
-        // InsetYBBox (glsl:86-91).  kFold: in come the ends of Y4, out go the reference's own ends (the site list at the top)
-        if constexpr (kFold) {
-                const float inset = __builtin_fmaf(mxY - mnY, 0.0078125f, -kInsetY);
-                mnY = clamp01(__builtin_fmaf(mnY, 0.25f, inset));
-                mxY = clamp01(__builtin_fmaf(mxY, 0.25f, -inset));
-        } else {
-                const float inset = (mxY - mnY) * 0.03125f - kInsetY;
-                mnY = clamp01(mnY + inset);
-                mxY = clamp01(mxY - inset);
-        }
+        // InsetYBBox (glsl:86-91): in come the ends of Y4, out go the reference's own ends (the site list ahead of the stage functions)
+        const float inset = __builtin_fmaf(mxY - mnY, 0.0078125f, -kInsetY);
+        mnY = clamp01(__builtin_fmaf(mnY, 0.25f, inset));
+        mxY = clamp01(__builtin_fmaf(mxY, 0.25f, -inset));
         // EmitAlphaEndPointsYCoCgDXT5 (glsl:252-259)
         uint32_t w0 = (round_u32<AWAY>(mnY * 255.0f) << 8) | round_u32<AWAY>(mxY * 255.0f);
         uint32_t w1 = 0;
@@ -786,35 +674,25 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 // device self-test); differences of byte-derived luma never fall in between, but the contract does not rest
                 // on that: a wave that sees such a value takes the IEEE division.
                 const float range = mxY - mnY;
-#ifdef UG_DXT_IEEE_DIV14 // A/B switch: the plain division
-                const float mid = range / 14.0f;
-#else
                 float mid = div14(range);
                 if (__builtin_expect(__any((__float_as_uint(range) - 1u) < (kDiv14Exact - 1u)), 0)) {
                         mid = range / 14.0f;
                 }
-#endif
-                // kFold: ab[k] = 4 x the reference's threshold, bit for bit, for the comparisons with Y4 below.  The ends, range and mid stay
+                // ab[k] = 4 x the reference's threshold, bit for bit, for the comparisons with Y4.  The ends, range and mid stay
                 // the reference's (so the range test, div14 and its route to the IEEE division are untouched: nothing here divides a
                 // scaled value); the 4 goes into the multipliers, RN(4 (8 - k) mx) = 4 RN((8 - k) mx), of which one per threshold is
                 // 4, 8 or 16 and rides in the fma of the sum; * inv7 scales with its operand, and + mid becomes fma(mid, 4, .).
                 // ab[1] = RN(4 mn + 4 mid) takes the one multiplication this form adds.
                 float ab[8];
-                if constexpr (kFold) {
-                        ab[1] = __builtin_fmaf(mid, 4.0f, mnY * 4.0f);
+                ab[1] = __builtin_fmaf(mid, 4.0f, mnY * 4.0f);
 #pragma unroll
-                        for (int k = 2; k <= 7; k++) {
-                                const float cx_ = (float) (4 * (8 - k)), cn_ = (float) (4 * (k - 1));
-                                const float sum = k <= 3 || k == 5 ? __builtin_fmaf(mnY, cn_, cx_ * mxY) : __builtin_fmaf(mxY, cx_, cn_ * mnY);
-                                ab[k] = __builtin_fmaf(mid, 4.0f, sum * inv7);
-                        }
-                } else {
-                        ab[1] = mnY + mid;
-#pragma unroll
-                        for (int k = 2; k <= 7; k++) {
-                                ab[k] = ((float) (8 - k) * mxY + (float) (k - 1) * mnY) * inv7 + mid;
-                        }
+                for (int k = 2; k <= 7; k++) {
+                        const float cx_ = (float) (4 * (8 - k)), cn_ = (float) (4 * (k - 1));
+                        const float sum = k <= 3 || k == 5 ? __builtin_fmaf(mnY, cn_, cx_ * mxY) : __builtin_fmaf(mxY, cx_, cn_ * mnY);
+                        ab[k] = __builtin_fmaf(mid, 4.0f, sum * inv7);
                 }
+
+                // EmitAlphaIndicesYCoCgDXT5 (glsl:262-312): count c = #{k : a <= ab_k}, index = f(c).  Y[] holds Y4 and ab[] 4 x the thresholds
                 // Thresholds in ascending order are T1..T7 = ab1, ab7, ab6, ab5, ab4, ab3, ab2 whenever they are
                 // monotone (always, except degenerate blocks whose clamped min == max).  For a monotone set the
                 // count is a 3-step binary search (3 compares + 4 selects instead of 7 compares + 7 adds); it is
@@ -826,20 +704,16 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 // so one compare decides for practically every block; only a wave that sees a narrower range evaluates the six
                 // explicit comparisons.
                 bool all_mono, all_wide = false; // both wave-uniform
-                (void) all_wide;
                 if (__builtin_expect(__all(range > 0.0009765625f), 1)) {
                         all_mono = true;
                         all_wide = true;
                 } else {
                         asm volatile("; explicit monotonicity check" ::: "memory");
-#if UG_DXT_FAST_INDEX
                         count_full_form(1);
-#endif
                         all_mono = __all((T1 <= T2) & (T2 <= T3) & (T3 <= T4) & (T4 <= T5) & (T5 <= T6) & (T6 <= T7));
                 }
                 // raw counts, 3 bits per pixel: lo = px 0..9 (30 bits), hi = px 10..15 (18 bits)
                 uint32_t lo = 0, hi = 0;
-#if UG_DXT_FAST_INDEX && !defined(UG_FORCE_ALPHA_LINEAR)
                 // Fast form of the same count, valid under the wave-uniform range > 2^-10 test above.  The thresholds sit range/7
                 // apart (+- 2^-21), so the position of a among them is known from ONE multiply-add up to the nearest threshold:
                 //   t = 7 - (a - mnY) * 7/range (clamped to [0, 8)) puts threshold T(8-m) at t = m - 1/2  (m = 1..7, descending thresholds D_m = T(8-m));
@@ -848,11 +722,10 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 //   c = #{m : a <= D_m} = g + (a <= D_(g+1)) -- and THAT comparison is the reference's own, on the reference's own
                 //   fp32 threshold (read back from the per-lane LDS column).  Row 7 = -inf serves g = 7 (a below every threshold).
                 // 1 fma + cvt + address + compare + 2 integer ops per pixel instead of 3 compares + 4 selects + 3 carries.
-                if (__builtin_expect(all_wide, 1)) {
+                if (!kForceAlphaLinear && __builtin_expect(all_wide, 1)) {
                         float *const ta = tab.alpha;
                         ta[0 * 64] = T7; ta[1 * 64] = T6; ta[2 * 64] = T5; ta[3 * 64] = T4;
                         ta[4 * 64] = T3; ta[5 * 64] = T2; ta[6 * 64] = T1; ta[7 * 64] = -__builtin_inff();
-#if UG_DXT_BITS_INDEX
                         // The same g without the conversion: u = (t - 1/2) / 7 = 6.5/7 - (a - mnY) / range with the clamp modifier (luma of
                         // YUV sources can lie far outside [mnY, mxY]), then r = fma(u, 7, 2^23): r is the integer 2^23 + RN(7 u), so the low
                         // bits of its pattern are g' = RN(clamp(t - 1/2, 0, 7)) = 0 .. 7.  g' = trunc(t) except where t is within its error
@@ -864,27 +737,17 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         // The pattern kIndexBits + g' is used as it is: << 8 (the row offset) drops kIndexBits altogether, and the
                         // index words collect it as a known sum that is subtracted once per word (the true words are 30 and 18 bits).
                         const float inv = __builtin_amdgcn_rcpf(range);
-                        // kFold: t as before from the reference's ends; the pixels are Y4, so their factor takes the 1/4 (exact: the same t)
-                        const float t0 = __builtin_fmaf(mnY, inv, (float) (6.5 / 7.0)), ninv = kFold ? inv * -0.25f : -inv;
-#else
-                        // t / 8 with the clamp modifier (luma of YUV sources can lie far outside [mnY, mxY]: g must stay in 0..7), then * (8 - ulp)
-                        const float inv = 0.875f * __builtin_amdgcn_rcpf(range);
-                        const float t0 = __builtin_fmaf(mnY, inv, 0.875f), ninv = kFold ? inv * -0.25f : -inv;
-#endif
-                        constexpr int kA = UG_DXT5_ALPHA_GROUP;
+                        // t as above from the reference's ends; the pixels are Y4, so their factor takes the 1/4 (exact: the same t)
+                        const float t0 = __builtin_fmaf(mnY, inv, (float) (6.5 / 7.0)), ninv = inv * -0.25f;
+                        constexpr int kA = kDxt5AlphaGroup;
 #pragma unroll
                         for (int h = 16 / kA - 1; h >= 0; h--) { // groups of kA pixels: kA table reads in flight, bounded register use
                                 float D[kA];
                                 uint32_t g[kA];
 #pragma unroll
                                 for (int j = kA - 1; j >= 0; j--) {
-#if UG_DXT_BITS_INDEX
                                         g[j] = __float_as_uint(__builtin_fmaf(clamp01(__builtin_fmaf(Y[kA * h + j], ninv, t0)), 7.0f, kIndexBias));
                                         D[j] = *(const float *) ((const char *) ta + (uint32_t) (g[j] << 8)); // rows of 64 floats
-#else
-                                        g[j] = cvt_u32_sat(clamp01(__builtin_fmaf(Y[kA * h + j], ninv, t0)) * 7.9999995f);
-                                        D[j] = ta[g[j] * 64];
-#endif
                                 }
                                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -895,17 +758,9 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                 }
                                 __builtin_amdgcn_sched_barrier(0);
                         }
-#if UG_DXT_BITS_INDEX
                         lo -= index_bias_sum(10, 3);
                         hi -= index_bias_sum(6, 3);
-#endif
-                } else
-#endif
-#ifdef UG_FORCE_ALPHA_LINEAR // test build: always take the reference-form path (tests/test_gpu_dxt.py)
-                if (all_mono && lo == 0xffffffffu) {
-#else
-                if (__builtin_expect(all_mono, 1)) {
-#endif
+                } else if (!kForceAlphaLinear && __builtin_expect(all_mono, 1)) {
 #pragma unroll
                         for (int i = 15; i >= 0; i--) {
                                 const float a = Y[i];
@@ -952,9 +807,8 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 w0 |= lo << 16;
                 w1 = (lo >> 16) | (hi << 14);
         }
-        // EmitIndicesYCoCgDXT5 (glsl:217-250).  The four squared distances of TWO horizontally adjacent
-        // pixels are computed with packed fp32 (v_pk_add/v_pk_mul: IEEE per component, so bit-identical to the
-        // scalar form); the kernel is VALU-issue bound and this halves the issue slots of its largest stage.
+
+        // EmitIndicesYCoCgDXT5 (glsl:217-250): the palette from the dequantised ends, then one 2-bit index per pixel
         uint32_t w_cidx = 0;
         {
                 const float q1 = (float) (1.0 / 3.0), q2 = (float) (2.0 / 3.0);
@@ -964,7 +818,6 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 cx[1] = cmn[0]; cy[1] = cmn[1];
                 cx[2] = lerp_w(cx[0], cx[1], w1, q1); cy[2] = lerp_w(cy[0], cy[1], w1, q1);
                 cx[3] = lerp_w(cx[0], cx[1], w2, q2); cy[3] = lerp_w(cy[0], cy[1], w2, q2);
-#if UG_DXT_FAST_INDEX
                 // Fast form (wave-uniform choice).  The palette lies on the segment c0 -> c1 in the order c0, c2, c3, c1 (s = 0, 1/3, 2/3, 1)
                 // and the index formula of glsl:237-244 is "nearest of the four": with s = the pixel's projection on the segment,
                 //   b2 = [d0 > d2] flips at s = 1/6, b0 = [d0 > d3] at 1/3, b4 = [d2 > d3] at 1/2, b1 = [d1 > d2] at 2/3, b3 = [d1 > d3] at 5/6,
@@ -982,7 +835,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 //   has vv >= 1.5e-5), and s itself is estimated to < 3e-4 (reciprocal + 5 roundings at magnitudes <= 650).
                 // A wave that holds a block outside that precondition (coincident end points over non-flat chroma) runs the full form below for all lanes.
                 //
-                // One location per chroma pair (PAIRS, UG_DXT_PAIR_ZONE).  The two pixels of a 4:2:2 pair come out of one yuv_pair_to_rgb
+                // One location per chroma pair (PAIRS).  The two pixels of a 4:2:2 pair come out of one yuv_pair_to_rgb
                 // call: U, V and the products rv, gu, gv, bu are shared, only the luma term differs, and it cancels in Co = (r - b) / 2 + off
                 // and Cg = (2 g - r - b) / 4 + off.  What is left is rounding: r, g, b, 2 g - r and (2 g - r) - b are rounded at magnitudes
                 // < 4 (<= 2^-23 each), r - b and the final sums at magnitudes < 2 (<= 2^-24), which adds up to
@@ -990,20 +843,20 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 // between the pixels of a pair (tests/test_dxt_pair_chroma_bound.py evaluates the statements in strict fp32 over every
                 // (U, V) and finds 2.4e-7 for both).  The projection moves by |dCo ka + dCg kb| <= 5e-7 * sqrt(2) / sqrt(vv) < 2.3e-4 of the
                 // segment with vv >= 1e-5.  So the zone found for the even pixel locates the odd one to < 3e-4 + 2.3e-4, and with the
-                // rounded row (UG_DXT_BITS_INDEX, below) to < 7e-4: m >= 1/12 - 7e-4 still leaves > 200 x the rounding error.
+                // rounded row (below) to < 7e-4: m >= 1/12 - 7e-4 still leaves > 200 x the rounding error.
                 // A pair that straddles 1/3 or 2/3 needs no care: there either zone's formula gives the same index (at 1/3: 2 b2 = 2 =
                 // 2 + b4, both 1/6 from their bisectors; at 2/3: 2 + b4 = 3 = 1 + 2 b3) -- the argument that lets a single pixel be
                 // placed in either zone.  Each pixel of the pair then evaluates ITS OWN open comparison against that palette pair,
                 // operands and order as in the reference.  The precondition below is the one of the per-pixel form: which waves take
                 // which form stays a property of the content.
                 //
-                // Row from float bits (UG_DXT_BITS_INDEX): u = (3 s - 1/2) / 2 with the clamp modifier, r = fma(u, 2, 2^23) is the integer
+                // Row from float bits: u = (3 s - 1/2) / 2 with the clamp modifier, r = fma(u, 2, 2^23) is the integer
                 // 2^23 + RN(clamp(3 s - 1/2, 0, 2)): zone 0 for 3 s < 1, 1 up to 2, 2 above -- trunc(3 s) except within the error of s
                 // around the borders (and RN's tie on them), which is the case of the paragraph above.  3/2 and -1/4 fold into ka, kb, kc.
                 // These fma only locate; no result of theirs is an operation of the reference.  kIndexBits << 10 (rows of 64 float4)
                 // is 0 mod 2^32, and the zone word collects kIndexBits as a known sum, subtracted once.
                 //
-                // One linear form per chroma pair (PAIRS, UG_DXT_PAIR_ZONE, UG_DXT_PAIR_LINEAR).  The open comparison keeps one bit, da > db,
+                // One linear form per chroma pair (PAIRS).  The open comparison keeps one bit, da > db,
                 // and in real arithmetic da - db = |p - A|^2 - |p - B|^2 is linear in the pixel p = (Co, Cg).  Half of it is
                 //   H(p) = (B - A) . (p - (A + B) / 2) = n . p + c,   n = B - A,   c = ((A - B) . (A + B)) / 2,
                 // and the rows of the table hold (m.x, m.y, c) of each zone's palette pair instead of (A, B): m = A - B = -n with one rounding
@@ -1029,7 +882,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 // db is L > 0.  Flat blocks are certified as they are: their word is replaced below.  A wave that holds an uncertified block
                 // (a pixel next to a bisector: smooth gradients put some there) writes the rows (A, B) over the linear ones -- the table does
                 // not grow -- and evaluates the reference's two distances for every pixel of all its blocks, in the zones already found:
-                // the parent's stage, operands and order.  These fma only locate; no result of theirs is an operation of the reference.
+                // the per-pixel form's stage, operands and order.  These fma only locate; no result of theirs is an operation of the reference.
                 const float vx = cx[1] - cx[0], vy = cy[1] - cy[0];
                 const float vv = vx * vx + vy * vy;
                 const float e0 = fmaxf(fmaxf(mxCo, cx[0]), cx[1]) - fminf(fminf(mnCo, cx[0]), cx[1]);
@@ -1040,7 +893,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 const bool flat = (mnCo == mxCo) & (mnCg == mxCg);
                 if (__builtin_expect(__all(((vv >= 1e-5f) & (vv * 256.0f > dmax)) | flat), 1)) {
                         float4 *const tc = tab.colour;
-                        constexpr bool kLinear = PAIRS && UG_DXT_PAIR_ZONE && UG_DXT_PAIR_LINEAR;
+                        constexpr bool kLinear = PAIRS;
                         auto write_rows = [&](float ax, float ay, float bx, float by, float cx2, float cy2, float cx3, float cy3) {
                                 tc[0 * 64] = make_float4(ax, ay, cx2, cy2);   // zone 0: d0 > d2
                                 tc[1 * 64] = make_float4(cx2, cy2, cx3, cy3); // zone 1: d2 > d3
@@ -1057,36 +910,25 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         } else {
                                 write_rows(cx[0], cy[0], cx[1], cy[1], cx[2], cy[2], cx[3], cy[3]);
                         }
-#if UG_DXT_BITS_INDEX
                         const float inv = 1.5f * __builtin_amdgcn_rcpf(vv);
                         const float ka = vx * inv, kb = vy * inv;
-                        // (kFold: kc locates only, so it may round twice instead of four times; s is then estimated no worse than above)
-                        const float kc = kFold ? __builtin_fmaf(-cx[0], ka, __builtin_fmaf(-cy[0], kb, -0.25f)) : -(cx[0] * ka + cy[0] * kb) - 0.25f;
-#else
-                        const float inv = __builtin_amdgcn_rcpf(vv);
-                        const float ka = vx * inv, kb = vy * inv;
-                        const float kc = -(cx[0] * ka + cy[0] * kb);
-#endif
+                        // (kc locates only, so it rounds twice, in two fma; s is then estimated no worse than above)
+                        const float kc = __builtin_fmaf(-cx[0], ka, __builtin_fmaf(-cy[0], kb, -0.25f));
                         uint32_t zones = 0, open = 0; // 2-bit zone per pixel; the open comparison's result, one bit per pixel
                         // groups of kC pixels, the table reads of the next group issued before the distances of this one
-                        constexpr int kC = UG_DXT5_FAST_GROUP, kGroups = 16 / kC;
-                        constexpr int kP = PAIRS && UG_DXT_PAIR_ZONE ? 2 : 1; // pixels per location
+                        constexpr int kC = kDxt5FastGroup, kGroups = 16 / kC;
+                        constexpr int kP = PAIRS ? 2 : 1; // pixels per location
                         static_assert(kC % kP == 0, "a group holds whole pairs");
                         float4 e[2][kC / kP];
                         uint32_t kk[2][kC / kP];
-                        [[maybe_unused]] float mag[kC / kP], least = __builtin_inff(); // kLinear: |L| of the group's pairs, the block's least
+                        float mag[kC / kP], least = __builtin_inff(); // kLinear: |L| of the group's pairs, the block's least
                         auto fetch = [&](int grp, int slot) {
 #pragma unroll
                                 for (int j = kC - kP; j >= 0; j -= kP) {
                                         const int i = kC * grp + j;
                                         const float s = clamp01(__builtin_fmaf(Co[i], ka, __builtin_fmaf(Cg[i], kb, kc)));
-#if UG_DXT_BITS_INDEX
                                         kk[slot][j / kP] = __float_as_uint(__builtin_fmaf(s, 2.0f, kIndexBias)); // kIndexBits + 0, 1, 2
                                         e[slot][j / kP] = *(const float4 *) ((const char *) tc + (uint32_t) (kk[slot][j / kP] << 10));
-#else
-                                        kk[slot][j / kP] = cvt_u32_sat(s * 2.9999998f); // 0, 1, 2
-                                        e[slot][j / kP] = tc[kk[slot][j / kP] * 64];
-#endif
                                 }
                         };
                         fetch(kGroups - 1, (kGroups - 1) & 1);
@@ -1123,9 +965,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                 }
                                 __builtin_amdgcn_sched_barrier(0);
                         }
-#if UG_DXT_BITS_INDEX
                         zones -= index_bias_sum(16 / kP, 2 * kP);
-#endif
                         if (kP == 2) { // pair j's zone sits in bits 4j, 4j + 1 = the field of pixel 2j: copy it to pixel 2j + 1's
                                 zones |= zones << 2;
                         }
@@ -1176,38 +1016,10 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                 }
                                 w_cidx = flat ? palette_index(d[0], d[1], d[2], d[3]) * 0x55555555u : w_cidx;
                         }
-                } else
-#endif
-                {
-                asm volatile("; colour index full form" ::: "memory");
-#if UG_DXT_FAST_INDEX
-                count_full_form(0);
-#endif
-                f32x2 cx2[4], cy2[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                        cx2[k] = (f32x2) { cx[k], cx[k] };
-                        cy2[k] = (f32x2) { cy[k], cy[k] };
-                }
-#pragma unroll
-                for (int i = 14; i >= 0; i -= 2) { // pixel pairs, last first: bits are shifted in MSB first
-                        const f32x2 co = { Co[i], Co[i + 1] }, cg = { Cg[i], Cg[i + 1] };
-                        f32x2 d[4];
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                                const f32x2 tx = co - cx2[k], ty = cg - cy2[k];
-                                d[k] = tx * tx + ty * ty;
-                        }
-#pragma unroll
-                        for (int h = 1; h >= 0; h--) { // pixel i+1, then pixel i
-                                const float d0 = d[0][h], d1 = d[1][h], d2 = d[2][h], d3 = d[3][h];
-                                // glsl:237-244
-                                const lanemask_t b0 = LANEMASK(d0 > d3), b1 = LANEMASK(d1 > d2), b2 = LANEMASK(d0 > d2),
-                                                 b3 = LANEMASK(d1 > d3), b4 = LANEMASK(d2 > d3);
-                                w_cidx = shift_in(w_cidx, (b1 & b2) | (b0 & b3)); // bit 2i+1
-                                w_cidx = shift_in(w_cidx, b0 & b4);               // bit 2i
-                        }
-                }
+                } else {
+                        asm volatile("; colour index full form" ::: "memory");
+                        count_full_form(0);
+                        w_cidx = emit_indices_ycocg_full_form(Co, Cg, cx, cy);
                 }
         }
 
@@ -1279,8 +1091,7 @@ __device__ __forceinline__ uint2 encode_dxt1(const Px16 &p, const IndexTables &t
                         c2[k] = lerp_w(c0[k], c1[k], w1, q1);
                         c3[k] = lerp_w(c0[k], c1[k], w2, q2);
                 }
-#if UG_DXT_FAST_INDEX
-                // Fast form, as in encode_dxt5ycocg (the argument does not depend on the number of components): zone of the pixel's
+                // Fast form, as in the fast colour stage of encode_dxt5ycocg (the argument does not depend on the number of components): zone of the pixel's
                 // projection on c0 -> c1, the one open comparison evaluated exactly as the reference does.  A distance of three squares
                 // is off by < 2^-21 dmax, still > 100 x below the smallest certain difference under the same precondition; a non-zero
                 // segment of 8-bit-expanded end points has vv >= 2.4e-4.  Coincident end points (flat blocks): full form for the wave.
@@ -1303,7 +1114,7 @@ __device__ __forceinline__ uint2 encode_dxt1(const Px16 &p, const IndexTables &t
                         const float kd = -((c0[0] * ka + c0[1] * kb) + c0[2] * kc);
                         uint32_t zones = 0, open = 0;
                         // groups of kG pixels; the table reads (2 x 12 bytes per pixel) of the next group are issued before the distances of this one
-                        constexpr int kG = UG_DXT1_FAST_GROUP;
+                        constexpr int kG = kDxt1FastGroup;
                         struct alignas(16) F3 { float x, y, z; };
                         F3 ea[2][kG], eb[2][kG];
                         uint32_t kk[2][kG];
@@ -1353,13 +1164,9 @@ __device__ __forceinline__ uint2 encode_dxt1(const Px16 &p, const IndexTables &t
                                 }
                                 w_idx = flat ? palette_index(d[0], d[1], d[2], d[3]) * 0x55555555u : w_idx;
                         }
-                } else
-#endif
-                {
+                } else {
                 asm volatile("; colour index full form" ::: "memory");
-#if UG_DXT_FAST_INDEX
                 count_full_form(0);
-#endif
                 const float *c[4] = { c0, c1, c2, c3 };
                 f32x2 cc[4][3];
 #pragma unroll
@@ -1381,11 +1188,7 @@ __device__ __forceinline__ uint2 encode_dxt1(const Px16 &p, const IndexTables &t
                         }
 #pragma unroll
                         for (int h = 1; h >= 0; h--) {
-                                const float d0 = d[0][h], d1 = d[1][h], d2 = d[2][h], d3 = d[3][h];
-                                const lanemask_t b0 = LANEMASK(d0 > d3), b1 = LANEMASK(d1 > d2), b2 = LANEMASK(d0 > d2),
-                                                 b3 = LANEMASK(d1 > d3), b4 = LANEMASK(d2 > d3);
-                                w_idx = shift_in(w_idx, (b1 & b2) | (b0 & b3));
-                                w_idx = shift_in(w_idx, b0 & b4);
+                                w_idx = shift_in_palette_index(w_idx, d[0][h], d[1][h], d[2][h], d[3][h]);
                         }
                 }
                 }
@@ -1401,46 +1204,31 @@ __device__ __forceinline__ uint2 encode_dxt1(const Px16 &p, const IndexTables &t
 // Occupancy target of the register allocator.  With the fast index stages the DXT5-YCoCg kernels need 100 VGPRs at 4 waves per SIMD
 // or 96 at 5 (the five dwords that do not fit are spilled in the rarely taken full-form colour stage only): 5 measures 2.4 % faster
 // (profiles/r03_fast_index_ab.txt).  The v210 kernels (three blocks per lane) keep the allocator's own choice.
-#ifndef UG_DXT_MIN_WAVES
-#define UG_DXT_MIN_WAVES (UG_DXT_FAST_INDEX ? 5 : 1)
-#endif
-#ifndef UG_DXT_ROWS_PER_WAVE
-#define UG_DXT_ROWS_PER_WAVE 1
-#endif
+constexpr int kMinWaves = 5;
 // A wave can walk kRowsPerWave consecutive block rows, issuing the loads of row j+1 before it encodes row j.
 // Measured on MI355X (interleaved A/B, 16 x 4K UYVY->DXT5): 1 row 0.2004 ms, 2 rows 0.2157, 4 rows 0.2224, 8 rows
-// 0.2230 -- the prefetching loop LOSES (VGPR 104 -> 126, no cross-row scheduling), so the default is one row per
-// wave and latency hiding is left to the 4 resident waves per SIMD.
-constexpr int kRowsPerWave = UG_DXT_ROWS_PER_WAVE;
+// 0.2230 -- the prefetching loop LOSES (VGPR 104 -> 126, no cross-row scheduling), so a wave encodes one row and
+// latency hiding is left to the resident waves.  With a trip count of one the loop and `nxt` compile to nothing.  They are still here only because
+// deleting them changed the instruction ORDER of the DXT5-YCoCg kernels (same instructions), and the change that fixed this constant had to leave the
+// compiler's output as it was; whoever next re-times these kernels can delete the loop.
+constexpr int kRowsPerWave = 1;
 
 template <int IN, int OUT, bool MIRROR, bool AWAY, bool EDGE>
-__global__ __launch_bounds__(256, (Loader<IN>::kBlocks > 1 ? 1 : UG_DXT_MIN_WAVES)) void dxt_encode_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
+__global__ __launch_bounds__(256, (Loader<IN>::kBlocks > 1 ? 1 : kMinWaves)) void dxt_encode_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
                                                          int units_per_row, int blocks_per_row, int block_rows, int height, uint32_t pitch,
                                                          size_t src_frame_stride, size_t dst_frame_stride, int width)
 {
         using L = Loader<IN>;
-        constexpr bool kTables = UG_DXT_FAST_INDEX, kAlpha = kTables && OUT == UG_DXT5_YCOCG;
+        constexpr bool kAlpha = OUT == UG_DXT5_YCOCG;
         constexpr int kColourRows = OUT == UG_DXT5_YCOCG ? 3 : 6;
         __shared__ float lds_alpha[kAlpha ? 4 * 8 * 64 : 1];
-        __shared__ float4 lds_colour[kTables ? 4 * kColourRows * 64 : 1];
+        __shared__ float4 lds_colour[4 * kColourRows * 64];
         IndexTables tab;
         {
                 const int wave = __builtin_amdgcn_readfirstlane(threadIdx.y);
                 tab.alpha = lds_alpha + (kAlpha ? wave * (8 * 64) + (int) threadIdx.x : 0);
-                tab.colour = lds_colour + (kTables ? wave * (kColourRows * 64) + (int) threadIdx.x : 0);
+                tab.colour = lds_colour + (wave * (kColourRows * 64) + (int) threadIdx.x);
         }
-#if UG_DXT_LDS_CONV
-        __shared__ ConvTables lds_conv;
-        if (IN == UG_PF_UYVY) { // 256 threads, one entry each: the statements of yuv_pair_to_rgb
-                const int b = (int) (threadIdx.y * 64 + threadIdx.x);
-                const float x = (float) b * kInv255;
-                const float U = x - 0.5f;
-                lds_conv.y[b] = 1.1643f * (x - 0.0625f);
-                lds_conv.v[b] = make_float2(1.7926f * U, 0.5328f * U);
-                lds_conv.u[b] = make_float2(0.2132f * U, 2.1124f * U);
-                __syncthreads();
-        }
-#endif
         // threadIdx.y is wave-uniform (a wave is one 64-lane row of the group): keep the block row, the row base
         // pointers and the bounds test on the scalar unit -- no per-lane 64-bit multiplies in the prologue.
         const int ux = blockIdx.x * 64 + threadIdx.x;
@@ -1471,9 +1259,6 @@ __global__ __launch_bounds__(256, (Loader<IN>::kBlocks > 1 ? 1 : UG_DXT_MIN_WAVE
                 ld.template load<EDGE>(src, pitch, ux, rows);
         };
         L cur, nxt;
-#if UG_DXT_LDS_CONV
-        if constexpr (IN == UG_PF_UYVY) { cur.lut = &lds_conv; nxt.lut = &lds_conv; }
-#endif
         load_row(cur, by0);
 #pragma unroll 1
         for (int j = 0; j < kRowsPerWave; j++) {
@@ -1575,14 +1360,14 @@ int launch(const EncodeJob &j)
                 return UG_HIP_EINVAL;
         }
         const dim3 block(64, wg_rows), grid((unsigned) ((upr + 63) / 64), (unsigned) ((brows + rows_per_group - 1) / rows_per_group), (unsigned) j.frames);
-#define UG_DXT_LAUNCH(MIRROR, EDGE) hipLaunchKernelGGL((dxt_encode_kernel<IN, OUT, MIRROR, AWAY, EDGE>), grid, block, 0, j.st, (const uint8_t *) j.src, \
+#define UG_LAUNCH_DXT(MIRROR, EDGE) hipLaunchKernelGGL((dxt_encode_kernel<IN, OUT, MIRROR, AWAY, EDGE>), grid, block, 0, j.st, (const uint8_t *) j.src, \
                                                       (uint8_t *) j.dst, upr, bpr, brows, h, (uint32_t) j.pitch, j.sfs, j.dfs, j.w)
         if (edge) {
-                if (mirror) UG_DXT_LAUNCH(true, true); else UG_DXT_LAUNCH(false, true);
+                if (mirror) UG_LAUNCH_DXT(true, true); else UG_LAUNCH_DXT(false, true);
         } else {
-                if (mirror) UG_DXT_LAUNCH(true, false); else UG_DXT_LAUNCH(false, false);
+                if (mirror) UG_LAUNCH_DXT(true, false); else UG_LAUNCH_DXT(false, false);
         }
-#undef UG_DXT_LAUNCH
+#undef UG_LAUNCH_DXT
         UG_HIP_LAUNCH_CHECK();
         return UG_HIP_SUCCESS;
 }
