@@ -156,6 +156,48 @@ def test_axis_rule():
     assert rs.lerp(np.int64(1), np.int64(2), 128) == 2
 
 
+@pytest.mark.parametrize("codec", [rs.RGBA, rs.UYVY])
+@pytest.mark.parametrize("merged", [False, True])
+@pytest.mark.parametrize("geom", [(67, 34, 45, 18), (64, 32, 48, 20), (33, 3, 7, 2), (131, 10, 128, 6)])
+@pytest.mark.parametrize("pad", [12, 48])
+def test_restatement_takes_a_source_pitch(codec, merged, geom, pad):
+    """lines `src_pitch` apart among random padding give exactly what the same lines give packed (the reference of the pitched and merged
+    cases of tests/test_gpu_scale_layouts.py), and the padding plays no part"""
+    w, h, ow, oh = geom
+    ls = rs.linesize(codec, w)
+    rng = np.random.default_rng(w + h + pad)
+    packed = rng.integers(0, 256, ls * h, dtype=np.uint8)
+    pitched = rng.integers(0, 256, (ls + pad) * h, dtype=np.uint8)
+    pitched.reshape(h, ls + pad)[:, :ls] = packed.reshape(h, ls)
+    want = rs.scale(packed, codec, w, h, ow, oh, merged)
+    assert np.array_equal(rs.scale(pitched, codec, w, h, ow, oh, merged, src_pitch=ls + pad), want)
+    pitched.reshape(h, ls + pad)[:, ls:] ^= 0xFF
+    assert np.array_equal(rs.scale(pitched, codec, w, h, ow, oh, merged, src_pitch=ls + pad), want)
+    assert not np.array_equal(rs.scale(pitched, codec, w, h, ow, oh, merged), want)  # (read as packed lines it is another picture)
+
+
+def test_two_texels_to_512_yield_every_weight():
+    """the shape of tests/test_gpu_scale_layouts.py::test_every_weight_pair: between texels 0 and 1, all 256 weights"""
+    i0, i1, wgt = rs.axis(2, 512)
+    assert set(wgt[(i0 == 0) & (i1 == 1)].tolist()) == set(range(256))
+
+
+def test_positions_fit_int64_at_the_size_limit():
+    """(2 x + 1) * n_in * 256 + n_out < 2^44 for a merged texture of 2 * 65536 texels; the first and last positions of the widest axes"""
+    assert (2 * (2 * 65536 - 1) + 1) * (2 * 65536) * 256 + 2 * 65536 < 2 ** 44
+    # the kernel's quotient (csrc/scale.hip: position): floor of the IEEE fp64 division of numerator by denominator.  Both are exact in
+    # fp64 and the nearest fraction below an integer n lies 1 / den under it, further than half an ulp of n while n * den < 2^53: the
+    # truncated quotient IS the floor on every axis the header accepts, the widest ones checked here
+    for n_in, n_out in ((131072, 4), (4, 131072), (131072, 131071), (131071, 131072), (65536, 65535), (65535, 65536), (65536, 1), (3, 65536)):
+        x = np.arange(n_out, dtype=np.int64)
+        num, den = (2 * x + 1) * n_in * 256 + n_out, 2 * n_out
+        assert np.array_equal((num.astype(np.float64) / np.float64(den)).astype(np.int64), num // den), (n_in, n_out)
+    i0, i1, w = rs.axis(131072, 4)
+    assert list(i0) == [16383, 49151, 81919, 114687] and list(i1) == [16384, 49152, 81920, 114688] and set(w) == {128}
+    i0, i1, w = rs.axis(4, 131072)
+    assert i0[0] == 0 and i1[0] == 0 and i0[-1] == 3 and i1[-1] == 3 and i0[65536] == 1 and i1[65536] == 2 and w[65536] == 128
+
+
 @pytest.mark.skipif(not os.path.exists(os.path.join(REF, "src", "vo_postprocess", "scale.c")) or shutil.which("gcc") is None
                     or not os.path.exists("/usr/lib/x86_64-linux-gnu/dri/swrast_dri.so"), reason="needs the reference tree and Mesa llvmpipe")
 def test_fixture_regenerates_from_the_reference():
