@@ -254,11 +254,11 @@ int ug_hip_selftest_dxt_encode(unsigned *mismatches, ug_hip_stream_t stream);
 int ug_hip_dxt_encode_stats(unsigned long long full_form_waves[2], int reset);
 /* The same with a third count.  From a 4:2:2 source (UYVY, v210) the DXT5-YCoCg encoder takes the sign of SelectYCoCgDiagonal's
  * covariance (glsl:169-183) from one product per chroma pair wherever an error bound decides it; a wave that holds a block the bound
- * does not decide forms the reference's 16-term sum for all of its blocks.  In the same way its colour stage takes the open comparison
- * of a chroma pair (glsl:231-244) from the sign of one linear form of the pair's even pixel wherever an error bound decides it for both
- * pixels; a wave that holds a block the bound does not decide evaluates the reference's two squared distances for every pixel of all of
- * its blocks.  counts[0 .. n - 1], n = 0 .. 4, receive { colour full form, alpha full form, waves that formed the reference's covariance
- * sum, waves that evaluated the per-pixel distances after the linear form }.  A reset through either function clears all four. */
+ * does not decide forms the reference's 16-term sum for all of its blocks.  In the same way its colour stage takes the colour index
+ * of a chroma pair (glsl:231-244) from the projection of the pair's even pixel on the palette segment wherever an error bound decides it
+ * for both pixels; a wave that holds a block the bound does not decide evaluates the reference's two squared distances for every pixel of
+ * all of its blocks.  counts[0 .. n - 1], n = 0 .. 4, receive { colour full form, alpha full form, waves that formed the reference's
+ * covariance sum, waves that evaluated the per-pixel distances after the projection }.  A reset through either function clears all four. */
 int ug_hip_dxt_encode_stats_ex(unsigned long long *counts, int n, int reset);
 /* Diagnostics (tests, profiling): what the last call of an LDGM session (below) issued -- kernel launches, host <-> device copies (the
  * schedule upload included) and levels of its decode schedule.  Any pointer may be NULL.  Does not touch the device. */

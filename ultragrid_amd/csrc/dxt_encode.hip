@@ -158,6 +158,9 @@ constexpr uint32_t index_bias_sum(int fields, int shift)
         for (int n = 0; n < fields && n * shift < 32; n++) s += kIndexBits << (n * shift);
         return s;
 }
+// DXT5-YCoCg colour stage, chroma pairs: the certificate of the index taken from the projection (derived at the stage),
+//   eps = (kProjEpsSeg sqrt(vv) + kProjEpsDiag sqrt(dmax) + kProjEpsDmax dmax) / vv,   in thirds of the palette segment
+constexpr float kProjEpsSeg = 8.5e-6f, kProjEpsDiag = 7.2e-6f, kProjEpsDmax = 4.3e-6f;
 // Diagnostics (ug_hip_dxt_encode_stats): waves that left a fast index stage for the reference's full form, counted in those (cold) paths only
 __device__ unsigned long long g_full_form_waves[2]; // [0] colour indices, [1] alpha indices
 __device__ __forceinline__ void count_full_form(int which)
@@ -175,7 +178,7 @@ __device__ __forceinline__ void count_exact_cov()
                 atomicAdd(&g_exact_cov_waves, 1ull);
         }
 }
-// and for the colour stage's linear form: waves that went on to the per-pixel distances.  That side is no rare
+// and for the colour stage's index from the projection: waves that went on to the per-pixel distances.  That side is no rare
 // path -- a few percent of the waves of ordinary video take it, all of them on content built for it -- and atomics on ONE address are served
 // one after the other: 129 600 counting waves per launch cost 1.4 ms beside 0.14 ms of encoding.  So the count is kept in kPairSlots
 // slots, each in a 128-byte line of its own, chosen by workgroup and wave; ug_hip_dxt_encode_stats_ex adds them up.
@@ -856,33 +859,41 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 // These fma only locate; no result of theirs is an operation of the reference.  kIndexBits << 10 (rows of 64 float4)
                 // is 0 mod 2^32, and the zone word collects kIndexBits as a known sum, subtracted once.
                 //
-                // One linear form per chroma pair (PAIRS).  The open comparison keeps one bit, da > db,
-                // and in real arithmetic da - db = |p - A|^2 - |p - B|^2 is linear in the pixel p = (Co, Cg).  Half of it is
-                //   H(p) = (B - A) . (p - (A + B) / 2) = n . p + c,   n = B - A,   c = ((A - B) . (A + B)) / 2,
-                // and the rows of the table hold (m.x, m.y, c) of each zone's palette pair instead of (A, B): m = A - B = -n with one rounding
-                // per component, c = fma(m.x, s.x, m.y * s.y) / 2 with s = A + B, about the origin of the colour space (no block-local
-                // origin: the coordinates are small, see below, and a local one costs two subtractions per pair).  The pair gets
-                //   L = fma(-Co, m.x, fma(-Cg, m.y, c))   on its EVEN pixel,   bit = L > 0   for both pixels,
-                // wherever |L| exceeds the sum of what separates L from half the reference's da - db of either pixel.  With u = 2^-24, d =
-                // |B - A| <= 0.334 sqrt(vv) (a third of the segment; c2 / c3 are off their ideal places by < 2e-7 against sqrt(vv) >= 3.1e-3),
-                // palette coordinates in [0, 1] and |Co|, |Cg| < 1.5 (the YUV front ends: Co = 128 / 255 +- 0.98, Cg = 128 / 255 +- 0.68):
-                //   rows and fma   n rounded: u d |p - (A + B) / 2| <= 2.5 u d (both lie in the box, whose diagonal is < 2.5);  s rounded
-                //                  at magnitudes <= 2, the product and the sum of c at <= |mx| + |my| each: u (2 |mx| + 3 |my|) <= 3.7 u d;
-                //                  the inner fma at <= 1.5 |my| + |mx| + |my|: <= 2.7 u d;  the outer one at |L| <= 2.5 d.  In all
-                //                  11.4 u d < 2.3e-7 sqrt(vv).
-                //   the pair       the odd pixel is within 5e-7 of the even one in Co and in Cg (above): |n . dp| <= sqrt(2) 5e-7 d
-                //                  < 2.4e-7 sqrt(vv).
+                // Index from the projection (PAIRS).  The four palette entries are colinear up to the rounding of c2 and c3, so the three
+                // bisectors of neighbouring entries are parallel, and in real arithmetic half of |p - A|^2 - |p - B|^2 across the bisector
+                // between the k-th and the (k + 1)-th entry along the segment is  H_k(p) = (vv / 9) (3 s - k - 1/2):  the projection again.
+                // Under the stage's precondition the index is "nearest of the four" (the zone argument above), so it is a function of
+                // the projection alone:  j = RN(clamp(3 s, 0, 3)) picks c0, c2, c3, c1 for j = 0 .. 3.  The pair gets
+                //   s = clamp(fma(Co, ka, fma(Cg, kb, kc)))   on its EVEN pixel,   k = v / vv,   kc = -(c0 . k) (rounded twice),
+                //   r = fma(s, 3, 2^23) = the integer 2^23 + j (float bits, as the rows),   dist = fma(s, 3, 2^23 - r) = 3 s - j,
+                // one 4-bit field per pair in a word, mapped to the index for all sixteen pixels at once (as map_fields does for alpha), and
+                // a block is certified where max |dist| < 1/2 - eps over its eight pairs: no pair within eps of a half-integer of 3 s.
+                // eps, in thirds of the segment, with u = 2^-24, l = sqrt(vv), |Co| < 1.5 and |Cg| < 1.2 (the YUV front ends: Co = 128 / 255
+                // +- 0.98, Cg = 128 / 255 +- 0.68), palette coordinates in [0, 1], so |ka|, |kb| <= 1 / l and |c0 . k| <= sqrt(2) / l:
+                //   evaluation     vv, its reciprocal (1 ulp) and the products by it are relative errors common to ka, kb, kc: they scale s
+                //                  about c0 by < 5 u, < 1e-6 of a third where s is in [0, 1].  ka, kb rounded, in the pixel's fma: (1.5 +
+                //                  1.2) u / l, in kc: 2 u / l;  kc's product and sum: (1 + 1.42) u / l;  the inner fma at magnitude <= (1.2 +
+                //                  1.42) / l: 2.6 u / l;  the outer one and the two of r and dist at magnitude <= 3: negligible beside these.
+                //                  9.7 u / l = 5.8e-7 / l in s, 1.75e-6 / l in thirds.
+                //   the pair       the odd pixel is within 3.5 * 2^-23 in Co and 4 * 2^-23 in Cg of the even one (the pair-location
+                //                  comment): |dp . k| <= 6.4e-7 / l in s, 1.9e-6 / l in thirds.
+                //   c2, c3         each coordinate is two products and a sum below 1 (2^-25, 2^-26, 2^-25) with weights off 1/3, 2/3 by
+                //                  < 4.5e-8: < 1.4e-7 per coordinate, delta < 2e-7 as a vector.  With n = B - A (ideal: v / 3) and m = (A + B) / 2,
+                //                  H = n . (p - m) moves by dn . (p - m) - n . dm:  |dn| <= 2 delta, |p - m| <= sqrt(dmax) (both in the box),
+                //                  |n . dm| <= (l / 3) delta.  Times 9 / vv:  3.6e-6 sqrt(dmax) / vv  (the tilt)  +  6e-7 / l  (the shift).
                 //   the reference  each of da, db is off by < 2^-22 dmax (the fast form's own argument, above), half their difference by
-                //                  < 2^-22 dmax.
-                // So |L - (da - db) / 2| < 4.7e-7 sqrt(vv) + 2^-22 dmax for either pixel, and a block is certified where the least |L| of
-                // its eight pairs exceeds
-                //   eps = 1e-6 sqrt(vv) + 2^-21 dmax,
-                // a factor > 2 over the analysis (tests/test_dxt_pair_linear_bound.py restates the stage in strict fp32 and finds the fp32 L
-                // within 0.05 eps of the one formed in double).  A certified L is not 0 and has the sign of da - db for both pixels, so da >
-                // db is L > 0.  Flat blocks are certified as they are: their word is replaced below.  A wave that holds an uncertified block
-                // (a pixel next to a bisector: smooth gradients put some there) writes the rows (A, B) over the linear ones -- the table does
-                // not grow -- and evaluates the reference's two distances for every pixel of all its blocks, in the zones already found:
-                // the per-pixel form's stage, operands and order.  These fma only locate; no result of theirs is an operation of the reference.
+                //                  < 2^-22 dmax:  2.15e-6 dmax / vv  in thirds.
+                // In all |3 s - k - 1/2 - 9 H_k / vv| < (4.25e-6 l + 3.6e-6 sqrt(dmax) + 2.15e-6 dmax) / vv for either pixel of the pair, and
+                //   eps = (8.5e-6 sqrt(vv) + 7.2e-6 sqrt(dmax) + 4.3e-6 dmax) / vv
+                // keeps a factor 2 over the analysis (tests/test_dxt_pair_projection_bound.py restates the stage in strict fp32 and finds the fp32
+                // projection within 0.05 eps of the one formed in double, and the projection margin within 0.04 eps of 9 H / vv).  A clamped s
+                // (a pixel beyond an end of the segment) has dist = 0: decided.  An exact tie has |dist| = 1/2 and is never certified:
+                // at 5/6 the reference's strict > gives c1 and RN could give either.  Flat blocks are certified as they are: their
+                // word is replaced below.  A wave that holds an uncertified block (a pixel next to a bisector: smooth gradients put some
+                // there) does what the stage did before the index came from the projection: it writes the rows (A, B), finds the zone of each
+                // pair from RN(clamp(3 s - 1/2, 0, 2)) (the constants of the row paragraph above, formed on that side only) and evaluates the
+                // reference's two distances for every pixel of all its blocks, operands and order as in the reference.  These fma only
+                // locate; no result of theirs is an operation of the reference.
                 const float vx = cx[1] - cx[0], vy = cy[1] - cy[0];
                 const float vv = vx * vx + vy * vy;
                 const float e0 = fmaxf(fmaxf(mxCo, cx[0]), cx[1]) - fminf(fminf(mnCo, cx[0]), cx[1]);
@@ -893,98 +904,59 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 const bool flat = (mnCo == mxCo) & (mnCg == mxCg);
                 if (__builtin_expect(__all(((vv >= 1e-5f) & (vv * 256.0f > dmax)) | flat), 1)) {
                         float4 *const tc = tab.colour;
-                        constexpr bool kLinear = PAIRS;
+                        constexpr bool kProjection = PAIRS;
                         auto write_rows = [&](float ax, float ay, float bx, float by, float cx2, float cy2, float cx3, float cy3) {
                                 tc[0 * 64] = make_float4(ax, ay, cx2, cy2);   // zone 0: d0 > d2
                                 tc[1 * 64] = make_float4(cx2, cy2, cx3, cy3); // zone 1: d2 > d3
                                 tc[2 * 64] = make_float4(bx, by, cx3, cy3);   // zone 2: d1 > d3
                         };
-                        if constexpr (kLinear) {
-                                auto linear_row = [&](int a, int b) { // (-n.x, -n.y, c) of H = half of |p - A|^2 - |p - B|^2, A = palette a, B = palette b
-                                        const float mx = cx[a] - cx[b], my = cy[a] - cy[b], sx = cx[a] + cx[b], sy = cy[a] + cy[b];
-                                        return make_float4(mx, my, 0.5f * __builtin_fmaf(mx, sx, my * sy), 0.0f);
-                                };
-                                tc[0 * 64] = linear_row(0, 2);
-                                tc[1 * 64] = linear_row(2, 3);
-                                tc[2 * 64] = linear_row(1, 3);
-                        } else {
-                                write_rows(cx[0], cy[0], cx[1], cy[1], cx[2], cy[2], cx[3], cy[3]);
-                        }
-                        const float inv = 1.5f * __builtin_amdgcn_rcpf(vv);
-                        const float ka = vx * inv, kb = vy * inv;
-                        // (kc locates only, so it rounds twice, in two fma; s is then estimated no worse than above)
-                        const float kc = __builtin_fmaf(-cx[0], ka, __builtin_fmaf(-cy[0], kb, -0.25f));
-                        uint32_t zones = 0, open = 0; // 2-bit zone per pixel; the open comparison's result, one bit per pixel
-                        // groups of kC pixels, the table reads of the next group issued before the distances of this one
-                        constexpr int kC = kDxt5FastGroup, kGroups = 16 / kC;
-                        constexpr int kP = PAIRS ? 2 : 1; // pixels per location
-                        static_assert(kC % kP == 0, "a group holds whole pairs");
-                        float4 e[2][kC / kP];
-                        uint32_t kk[2][kC / kP];
-                        float mag[kC / kP], least = __builtin_inff(); // kLinear: |L| of the group's pairs, the block's least
-                        auto fetch = [&](int grp, int slot) {
+                        if constexpr (kProjection) {
+                                const float rvv = __builtin_amdgcn_rcpf(vv);
+                                const float ka = vx * rvv, kb = vy * rvv;
+                                // (kc locates only, so it rounds twice; the derivation above counts both)
+                                const float kc = __builtin_fmaf(-cx[0], ka, -cy[0] * kb);
+                                uint32_t jw = 0;      // kIndexBits + j per pair, 4 bits apart
+                                float worst = 0.0f;   // the block's largest |3 s - j|
 #pragma unroll
-                                for (int j = kC - kP; j >= 0; j -= kP) {
-                                        const int i = kC * grp + j;
-                                        const float s = clamp01(__builtin_fmaf(Co[i], ka, __builtin_fmaf(Cg[i], kb, kc)));
-                                        kk[slot][j / kP] = __float_as_uint(__builtin_fmaf(s, 2.0f, kIndexBias)); // kIndexBits + 0, 1, 2
-                                        e[slot][j / kP] = *(const float4 *) ((const char *) tc + (uint32_t) (kk[slot][j / kP] << 10));
-                                }
-                        };
-                        fetch(kGroups - 1, (kGroups - 1) & 1);
+                                for (int grp = 3; grp >= 0; grp--) { // two pairs per step: one v_max3_f32 with abs modifiers
+                                        float dist[2];
 #pragma unroll
-                        for (int grp = kGroups - 1; grp >= 0; grp--) {
-                                const int slot = grp & 1;
-                                if (grp > 0) {
-                                        fetch(grp - 1, slot ^ 1);
-                                }
-                                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                                for (int j = kC - 1; j >= 0; j--) {
-                                        const int i = kC * grp + j;
-                                        const float4 q = e[slot][j / kP];
-                                        if constexpr (kLinear) { // one bit per PAIR: open collects eight
-                                                if (j % kP == 0) {
-                                                        const float L = __builtin_fmaf(-Co[i], q.x, __builtin_fmaf(-Cg[i], q.y, q.z)); // negations ride as operand modifiers
-                                                        zones = (zones << (2 * kP)) + kk[slot][j / kP];
-                                                        open = shift_in(open, LANEMASK(L > 0.0f));
-                                                        mag[j / kP] = fabsf(L);
-                                                }
-                                        } else {
-                                                const float ax = Co[i] - q.x, ay = Cg[i] - q.y, bx = Co[i] - q.z, by = Cg[i] - q.w;
-                                                const float da = ax * ax + ay * ay, db = bx * bx + by * by; // glsl:231-235, same operation order
-                                                if (j % kP == 0) { // one field of 2 * kP bits per location
-                                                        zones = (zones << (2 * kP)) + kk[slot][j / kP];
-                                                }
-                                                open = shift_in(open, LANEMASK(da > db));
+                                        for (int h = 1; h >= 0; h--) {
+                                                const int i = 4 * grp + 2 * h;
+                                                const float s = clamp01(__builtin_fmaf(Co[i], ka, __builtin_fmaf(Cg[i], kb, kc)));
+                                                const float r = __builtin_fmaf(s, 3.0f, kIndexBias); // the integer 2^23 + j
+                                                jw = (jw << 4) + __float_as_uint(r);
+                                                dist[h] = __builtin_fmaf(s, 3.0f, kIndexBias - r);   // 3 s - j: the difference is exact
                                         }
+                                        worst = fmaxf(fmaxf(worst, fabsf(dist[0])), fabsf(dist[1]));
                                 }
-                                if constexpr (kLinear) { // v_min3_f32 with abs modifiers: one per group
-                                        static_assert(kC / kP == 2, "two pairs per group");
-                                        least = fminf(fminf(least, mag[0]), mag[1]);
-                                }
-                                __builtin_amdgcn_sched_barrier(0);
-                        }
-                        zones -= index_bias_sum(16 / kP, 2 * kP);
-                        if (kP == 2) { // pair j's zone sits in bits 4j, 4j + 1 = the field of pixel 2j: copy it to pixel 2j + 1's
-                                zones |= zones << 2;
-                        }
-                        uint32_t c;
-                        if constexpr (kLinear) {
-                                const float eps = __builtin_fmaf(dmax, 4.76837158203125e-07f, 1e-6f * __builtin_amdgcn_sqrtf(vv)); // 2^-21 dmax + 1e-6 sqrt(vv)
-                                const lanemask_t certain = LANEMASK(least > eps) | LANEMASK(flat);
+                                const float sd = __builtin_amdgcn_sqrtf(dmax);
+                                const float eps = __builtin_fmaf(sd, __builtin_fmaf(sd, kProjEpsDmax, kProjEpsDiag), kProjEpsSeg * __builtin_amdgcn_sqrtf(vv)) * rvv;
+                                const lanemask_t certain = LANEMASK(worst < 0.5f - eps) | LANEMASK(flat);
                                 if (__builtin_expect(certain == LANEMASK(true), 1)) { // __all, on the two comparisons' own lane masks
-                                        // pair j's bit from bit j to bit 4j = the field of pixel 2j, then to pixel 2j + 1's as well
-                                        c = (open | (open << 12)) & 0x000f000fu;
-                                        c = (c | (c << 6)) & 0x03030303u;
-                                        c = (c | (c << 3)) & 0x11111111u;
-                                        c |= c << 2;
+                                        jw -= index_bias_sum(8, 4);
+                                        jw |= jw << 2; // pair j's field to pixel 2j + 1's as well
+                                        // j -> index, all sixteen fields at once: 0 -> 0, 1 -> 2, 2 -> 3, 3 -> 1, that is bit 0 = j1, bit 1 = j1 ^ j0
+                                        const uint32_t j1 = (jw >> 1) & 0x55555555u;
+                                        w_cidx = j1 | (((jw ^ j1) & 0x55555555u) << 1);
                                 } else {
-                                        // The empty asm keeps this a real branch (see the alpha stage's fallback).
-                                        asm volatile("; per-pixel distances" ::: "memory");
+                                        // The empty asm keeps this a real branch (see the alpha stage's fallback); vv passes through it so that
+                                        // this side forms its own reciprocal and constants: nothing of it is computed ahead of the branch.
+                                        float vw = vv;
+                                        asm volatile("; per-pixel distances" : "+v"(vw) :: "memory");
                                         count_exact_pair();
                                         write_rows(cx[0], cy[0], cx[1], cy[1], cx[2], cy[2], cx[3], cy[3]);
-                                        open = 0;
+                                        const float inv = 1.5f * __builtin_amdgcn_rcpf(vw);
+                                        const float za = vx * inv, zb = vy * inv;
+                                        const float zc = __builtin_fmaf(-cx[0], za, __builtin_fmaf(-cy[0], zb, -0.25f));
+                                        uint32_t zones = 0, open = 0; // 2-bit zone per pixel; the open comparison's result, one bit per pixel
+#pragma unroll
+                                        for (int i = 14; i >= 0; i -= 2) {
+                                                const float s = clamp01(__builtin_fmaf(Co[i], za, __builtin_fmaf(Cg[i], zb, zc)));
+                                                zones = (zones << 4) + __float_as_uint(__builtin_fmaf(s, 2.0f, kIndexBias)); // kIndexBits + 0, 1, 2
+                                        }
+                                        zones -= index_bias_sum(8, 4);
+                                        zones |= zones << 2; // pair j's zone sits in bits 4j, 4j + 1 = the field of pixel 2j: copy it to pixel 2j + 1's
 #pragma unroll
                                         for (int i = 15; i >= 0; i--) { // the pixel's zone sits in bits 2 i, 2 i + 1; a row is 64 float4
                                                 const float4 q = *(const float4 *) ((const char *) tc + (((zones >> (2 * i)) & 3u) << 10));
@@ -992,17 +964,58 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                                 const float da = ax * ax + ay * ay, db = bx * bx + by * by; // glsl:231-235, same operation order
                                                 open = shift_in(open, LANEMASK(da > db));
                                         }
-                                        c = spread16(open);
+                                        const uint32_t c = spread16(open);
+                                        const uint32_t k0 = zones & 0x55555555u, k1 = (zones >> 1) & 0x55555555u;
+                                        w_cidx = ((k0 & c) | k1) | ((k0 | c) << 1);
                                 }
                         } else {
-                                c = spread16(open);
+                                write_rows(cx[0], cy[0], cx[1], cy[1], cx[2], cy[2], cx[3], cy[3]);
+                                const float inv = 1.5f * __builtin_amdgcn_rcpf(vv);
+                                const float ka = vx * inv, kb = vy * inv;
+                                // (kc locates only, so it rounds twice, in two fma; s is then estimated no worse than above)
+                                const float kc = __builtin_fmaf(-cx[0], ka, __builtin_fmaf(-cy[0], kb, -0.25f));
+                                uint32_t zones = 0, open = 0; // 2-bit zone per pixel; the open comparison's result, one bit per pixel
+                                // groups of kC pixels, the table reads of the next group issued before the distances of this one
+                                constexpr int kC = kDxt5FastGroup, kGroups = 16 / kC;
+                                float4 e[2][kC];
+                                uint32_t kk[2][kC];
+                                auto fetch = [&](int grp, int slot) {
+#pragma unroll
+                                        for (int j = kC - 1; j >= 0; j--) {
+                                                const int i = kC * grp + j;
+                                                const float s = clamp01(__builtin_fmaf(Co[i], ka, __builtin_fmaf(Cg[i], kb, kc)));
+                                                kk[slot][j] = __float_as_uint(__builtin_fmaf(s, 2.0f, kIndexBias)); // kIndexBits + 0, 1, 2
+                                                e[slot][j] = *(const float4 *) ((const char *) tc + (uint32_t) (kk[slot][j] << 10));
+                                        }
+                                };
+                                fetch(kGroups - 1, (kGroups - 1) & 1);
+#pragma unroll
+                                for (int grp = kGroups - 1; grp >= 0; grp--) {
+                                        const int slot = grp & 1;
+                                        if (grp > 0) {
+                                                fetch(grp - 1, slot ^ 1);
+                                        }
+                                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                                        for (int j = kC - 1; j >= 0; j--) {
+                                                const int i = kC * grp + j;
+                                                const float4 q = e[slot][j];
+                                                const float ax = Co[i] - q.x, ay = Cg[i] - q.y, bx = Co[i] - q.z, by = Cg[i] - q.w;
+                                                const float da = ax * ax + ay * ay, db = bx * bx + by * by; // glsl:231-235, same operation order
+                                                zones = (zones << 2) + kk[slot][j];
+                                                open = shift_in(open, LANEMASK(da > db));
+                                        }
+                                        __builtin_amdgcn_sched_barrier(0);
+                                }
+                                zones -= index_bias_sum(16, 2);
+                                const uint32_t c = spread16(open);
+                                const uint32_t k0 = zones & 0x55555555u, k1 = (zones >> 1) & 0x55555555u;
+                                w_cidx = ((k0 & c) | k1) | ((k0 | c) << 1);
                         }
-                        const uint32_t k0 = zones & 0x55555555u, k1 = (zones >> 1) & 0x55555555u;
-                        w_cidx = ((k0 & c) | k1) | ((k0 | c) << 1);
                         if (__any(flat)) {
                                 asm volatile("; flat blocks" ::: "memory");
                                 float4 p02, p13; // the palette, back from the table (not kept in registers) where the table holds it
-                                if constexpr (kLinear) {
+                                if constexpr (kProjection) {
                                         p02 = make_float4(cx[0], cy[0], cx[2], cy[2]); p13 = make_float4(cx[1], cy[1], cx[3], cy[3]);
                                 } else {
                                         p02 = tc[0 * 64]; p13 = tc[2 * 64];
@@ -1544,7 +1557,7 @@ extern "C" int ug_hip_dxt_encode_stats(unsigned long long full_form_waves[2], in
 }
 
 // The same with the counters of the certified stages: counts[0 .. n - 1] of { colour full form, alpha full form, exact covariance sum,
-// per-pixel distances after the colour stage's linear form }
+// per-pixel distances after the colour stage's projection }
 extern "C" int ug_hip_dxt_encode_stats_ex(unsigned long long *counts, int n, int reset)
 {
         if (n < 0 || n > 4 || (n > 0 && !counts)) return UG_HIP_EINVAL;
