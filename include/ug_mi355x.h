@@ -260,6 +260,14 @@ int ug_hip_dxt_encode_stats(unsigned long long full_form_waves[2], int reset);
  * all of its blocks.  counts[0 .. n - 1], n = 0 .. 4, receive { colour full form, alpha full form, waves that formed the reference's
  * covariance sum, waves that evaluated the per-pixel distances after the projection }.  A reset through either function clears all four. */
 int ug_hip_dxt_encode_stats_ex(unsigned long long *counts, int n, int reset);
+/* A fifth count, through an entry point of its own (the one above keeps refusing n > 4).  From a 4:2:2 source the DXT5-YCoCg encoder
+ * takes the 3-bit alpha count of a pixel (glsl:262-312) from the pixel's location among the thresholds, RN(7 - (a - min) * 7 / range),
+ * wherever an error bound keeps every pixel of the block away from a threshold; a wave that holds a block the bound does not decide
+ * forms the reference's thresholds and evaluates the reference's comparison for every pixel of all of its blocks.  *exact_waves (may be
+ * NULL) receives the number of such waves since the last reset on the current device.  Content with flat chroma and few luma levels
+ * puts a pixel on the middle threshold in most blocks: there every wave counts.  A reset through any of the three functions clears all
+ * five counts.  Synchronises the device. */
+int ug_hip_dxt_encode_stats_alpha(unsigned long long *exact_waves, int reset);
 /* Diagnostics (tests, profiling): what the last call of an LDGM session (below) issued -- kernel launches, host <-> device copies (the
  * schedule upload included) and levels of its decode schedule.  Any pointer may be NULL.  Does not touch the device. */
 typedef struct ug_hip_ldgm ug_hip_ldgm;

@@ -191,6 +191,20 @@ __device__ __forceinline__ void count_exact_pair()
                 atomicAdd(&g_exact_pair_waves[slot * kPairSlotStride], 1ull);
         }
 }
+// and for the alpha stage's count from the location (chroma-pair loaders): waves that went on to the thresholds and the reference's
+// comparison.  A few percent of the waves of ordinary video, every wave of content with few luma levels, so slots as above
+// (ug_hip_dxt_encode_stats_alpha adds them up).
+__device__ unsigned long long g_exact_alpha_waves[kPairSlots * kPairSlotStride];
+__device__ __forceinline__ void count_exact_alpha()
+{
+        if ((int) threadIdx.x == __builtin_amdgcn_readfirstlane((int) threadIdx.x)) {
+                const uint32_t slot = ((blockIdx.x + 17u * blockIdx.y + 101u * blockIdx.z) * 4u + threadIdx.y) & (kPairSlots - 1);
+                atomicAdd(&g_exact_alpha_waves[slot * kPairSlotStride], 1ull);
+        }
+}
+// DXT5-YCoCg alpha stage, chroma pairs: the certificate of the count taken from the location (derived at the stage),
+//   eps = kAlphaEpsFixed + kAlphaEpsRange / range,   in steps of range / 7
+constexpr float kAlphaEpsFixed = 2.2e-6f, kAlphaEpsRange = 5.7e-6f;
 struct IndexTables {
         float *alpha;   // [8][64] floats: thresholds in DESCENDING order, row 7 = -inf
         float4 *colour;   // DXT5-YCoCg: [3][64] (A.x, A.y, B.x, B.y) of the palette pair whose bisector crosses zone k; DXT1: [6][64], rows 2k / 2k + 1 = A / B (xyz)
@@ -672,125 +686,190 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
         uint32_t w1 = 0;
         // EmitAlphaIndicesYCoCgDXT5 (glsl:262-312): count c = #{k : a <= ab_k}, index = f(c).
         {
-                const float inv7 = (float) (1.0 / 7.0);
-                // (mxY - mnY) / 14.0f.  div14() is bit-identical to the division for x = 0 and for every x >= 2^-100 (exhaustive
-                // device self-test); differences of byte-derived luma never fall in between, but the contract does not rest
-                // on that: a wave that sees such a value takes the IEEE division.
-                const float range = mxY - mnY;
-                float mid = div14(range);
-                if (__builtin_expect(__any((__float_as_uint(range) - 1u) < (kDiv14Exact - 1u)), 0)) {
-                        mid = range / 14.0f;
-                }
-                // ab[k] = 4 x the reference's threshold, bit for bit, for the comparisons with Y4.  The ends, range and mid stay
-                // the reference's (so the range test, div14 and its route to the IEEE division are untouched: nothing here divides a
-                // scaled value); the 4 goes into the multipliers, RN(4 (8 - k) mx) = 4 RN((8 - k) mx), of which one per threshold is
-                // 4, 8 or 16 and rides in the fma of the sum; * inv7 scales with its operand, and + mid becomes fma(mid, 4, .).
-                // ab[1] = RN(4 mn + 4 mid) takes the one multiplication this form adds.
-                float ab[8];
-                ab[1] = __builtin_fmaf(mid, 4.0f, mnY * 4.0f);
-#pragma unroll
-                for (int k = 2; k <= 7; k++) {
-                        const float cx_ = (float) (4 * (8 - k)), cn_ = (float) (4 * (k - 1));
-                        const float sum = k <= 3 || k == 5 ? __builtin_fmaf(mnY, cn_, cx_ * mxY) : __builtin_fmaf(mxY, cx_, cn_ * mnY);
-                        ab[k] = __builtin_fmaf(mid, 4.0f, sum * inv7);
-                }
-
-                // EmitAlphaIndicesYCoCgDXT5 (glsl:262-312): count c = #{k : a <= ab_k}, index = f(c).  Y[] holds Y4 and ab[] 4 x the thresholds
-                // Thresholds in ascending order are T1..T7 = ab1, ab7, ab6, ab5, ab4, ab3, ab2 whenever they are
-                // monotone (always, except degenerate blocks whose clamped min == max).  For a monotone set the
-                // count is a 3-step binary search (3 compares + 4 selects instead of 7 compares + 7 adds); it is
-                // the SAME function of (a, ab[]) as the reference's linear count, so results stay bit-identical.
-                const float T1 = ab[1], T2 = ab[7], T3 = ab[6], T4 = ab[5], T5 = ab[4], T6 = ab[3], T7 = ab[2];
-                // Monotone for sure when the clamped range exceeds 2^-10: consecutive thresholds are range/7 apart in exact
-                // arithmetic and each carries < 2^-22 of rounding error (operands <= 7, results <= 1), so 2^-10/7 of spacing
-                // cannot be overturned.  After the inset the range is >= 16/255/16 unless both ends clamp to the same bound,
-                // so one compare decides for practically every block; only a wave that sees a narrower range evaluates the six
-                // explicit comparisons.
-                bool all_mono, all_wide = false; // both wave-uniform
-                if (__builtin_expect(__all(range > 0.0009765625f), 1)) {
-                        all_mono = true;
-                        all_wide = true;
-                } else {
-                        asm volatile("; explicit monotonicity check" ::: "memory");
-                        count_full_form(1);
-                        all_mono = __all((T1 <= T2) & (T2 <= T3) & (T3 <= T4) & (T4 <= T5) & (T5 <= T6) & (T6 <= T7));
-                }
                 // raw counts, 3 bits per pixel: lo = px 0..9 (30 bits), hi = px 10..15 (18 bits)
                 uint32_t lo = 0, hi = 0;
-                // Fast form of the same count, valid under the wave-uniform range > 2^-10 test above.  The thresholds sit range/7
-                // apart (+- 2^-21), so the position of a among them is known from ONE multiply-add up to the nearest threshold:
-                //   t = 7 - (a - mnY) * 7/range (clamped to [0, 8)) puts threshold T(8-m) at t = m - 1/2  (m = 1..7, descending thresholds D_m = T(8-m));
-                //   g = trunc(t) (saturating at 0): every D_m with m <= g lies >= 0.49 steps above a, every D_m with m >= g + 2 lies
-                //   >= 0.49 steps below it (error of t < 6e-4 steps: rcp 1 ulp, mnY*inv rounded at magnitude <= 7168, fma rounding), so
-                //   c = #{m : a <= D_m} = g + (a <= D_(g+1)) -- and THAT comparison is the reference's own, on the reference's own
-                //   fp32 threshold (read back from the per-lane LDS column).  Row 7 = -inf serves g = 7 (a below every threshold).
-                // 1 fma + cvt + address + compare + 2 integer ops per pixel instead of 3 compares + 4 selects + 3 carries.
-                if (!kForceAlphaLinear && __builtin_expect(all_wide, 1)) {
-                        float *const ta = tab.alpha;
-                        ta[0 * 64] = T7; ta[1 * 64] = T6; ta[2 * 64] = T5; ta[3 * 64] = T4;
-                        ta[4 * 64] = T3; ta[5 * 64] = T2; ta[6 * 64] = T1; ta[7 * 64] = -__builtin_inff();
-                        // The same g without the conversion: u = (t - 1/2) / 7 = 6.5/7 - (a - mnY) / range with the clamp modifier (luma of
-                        // YUV sources can lie far outside [mnY, mxY]), then r = fma(u, 7, 2^23): r is the integer 2^23 + RN(7 u), so the low
-                        // bits of its pattern are g' = RN(clamp(t - 1/2, 0, 7)) = 0 .. 7.  g' = trunc(t) except where t is within its error
-                        // (< 6e-4 steps as above: rcp 1 ulp, mnY * inv rounded at magnitude <= 1024, two fma roundings) of an integer, or
-                        // exactly on it, where g' may be the neighbour of trunc(t).  There a lies 1/2 step from both nearest thresholds and
-                        // both rows give the same count: row g: g + (a <= D_(g+1)) = g + 1 (D_(g+1) is 1/2 step ABOVE a), row g + 1:
-                        // g + 1 + (a <= D_(g+2)) = g + 1 (D_(g+2) is 1/2 step BELOW a) -- the 0.49-step argument above covers either.
-                        // These fma are locating arithmetic only: no result of theirs is an operation of the reference.
-                        // The pattern kIndexBits + g' is used as it is: << 8 (the row offset) drops kIndexBits altogether, and the
-                        // index words collect it as a known sum that is subtracted once per word (the true words are 30 and 18 bits).
-                        const float inv = __builtin_amdgcn_rcpf(range);
-                        // t as above from the reference's ends; the pixels are Y4, so their factor takes the 1/4 (exact: the same t)
-                        const float t0 = __builtin_fmaf(mnY, inv, (float) (6.5 / 7.0)), ninv = inv * -0.25f;
-                        constexpr int kA = kDxt5AlphaGroup;
+                float range = mxY - mnY;
+                bool located = false; // wave-uniform: lo / hi hold the counts already
+                // Count from the location alone (chroma-pair loaders).  In the notation of the fast form below: the thresholds are D_m,
+                // descending, range / 7 apart, with a <= D_m <=> t >= m - 1/2 for t = 7 - (a - mnY) * 7 / range in real arithmetic on the
+                // reference's fp32 ends and range, so the reference's count #{m : a <= D_m} is RN(clamp(t, 0, 7)) wherever t is not next to a
+                // half-integer.  The pixels are Y4 (their factor takes the exact 1/4):
+                //   u = clamp01(fma(Y4, -inv / 4, fma(mnY, inv, 1))) = t / 7,   inv = rcp(range),
+                //   r = fma(u, 7, 2^23) = the integer 2^23 + c, c = RN(7 u) = 0 .. 7 (float bits, collected as the rows below are),
+                //   dist = fma(u, 7, 2^23 - r) = 7 u - c  (the difference is exact),
+                // and a block is certified where max |dist| < 1/2 - eps over its sixteen pixels: no pixel within eps of a half-integer of t.
+                // eps, in steps of range / 7, with R = range (fp32), mnY, mxY in [0, 1] and R > 2^-10 (the wave test in front):
+                //   the reference's thresholds   4 D_m as formed below against the real 4 mnY + 4 R (15 - 2 m) / 14 (the 4x domain, one step =
+                //                  4 R / 7, so an absolute error E there is 1.75 E / R steps): the product (8 - k) 4 mxY or (k - 1) 4 mnY <= 24 and
+                //                  the sum <= 28 round by <= 2^-20 each, and * 1/7 leaves (2^-19) / 7 = 2.7e-7;  RN(1/7) is off by 4.5e-8
+                //                  relative, on a quotient <= 4: 1.8e-7;  the quotient's and the final fma's rounding at magnitude <= 4: 2^-23
+                //                  = 1.2e-7 each;  mid = RN(R / 14) <= 1/14 by 2^-28, times 4: 1.5e-8;  the sum carries mxY - mnY where mid carries
+                //                  R = RN(mxY - mnY): (6/7) 4 * 2^-25 = 1.0e-7.  E <= 8.1e-7: 1.41e-6 / R.  (D_7 = fma(mid, 4, 4 mnY) rounds once.)
+                //   inv            rcp at 1 ulp scales t about 7 (a = mnY) by 2^-23: (a - mnY) / R <= 1 where a threshold is, 7 * 2^-23 = 8.3e-7.
+                //   t0             fma(mnY, inv, 1) rounds at magnitude 1 + mnY / R <= 1 / R (mnY <= 1 - R): 2^-24 / R, times 7 = 4.2e-7 / R.
+                //   the pixel's fma  one rounding of a result in [0, 1]: 7 * 2^-25 = 2.1e-7.  r is exact (that IS RN), dist rounds at <= 1/2
+                //                  (1.5e-8), and so does 1/2 - eps (3e-8).
+                // In all |7 u - (t of the reference's own comparison)| < 1.09e-6 + 1.83e-6 / R.  A factor 2 over that is 2.2e-6 + 3.7e-6 / R;
+                // the 1 / R part is set larger, so that the thresholds' term ALONE (1.41e-6 / R, three quarters of the whole for small R)
+                // keeps a factor 4, as the location's terms (1.09e-6 + 0.42e-6 / R) then do as well:
+                //   eps = 2.2e-6 + 5.7e-6 / R      (kAlphaEpsFixed, kAlphaEpsRange)
+                // (tests/test_dxt_alpha_location_bound.py restates the stage in strict fp32 and holds each of the two to eps / 4).  The
+                // mnY / R term is a seventh of the 1 / R part, so the pixels are not shifted by 4 mnY first (one more instruction each).
+                // A clamped u (luma beyond an inset end) has dist = 0: decided, c = 0 or 7 as the reference counts.  An exact tie has
+                // |dist| = 1/2 and is never certified: the reference's <= counts it, RN to even may not.  A wave that holds an
+                // uncertified block does what the stage does for every other loader: thresholds, rows, g' and the reference's own
+                // comparison for every pixel of all its blocks, from operands that pass through the empty asm so that nothing of that
+                // side is formed ahead of the branch.  These fma only locate; no result of theirs is an operation of the reference.
+                if constexpr (PAIRS && !kForceAlphaLinear) {
+                        if (__builtin_expect(__all(range > 0.0009765625f), 1)) {
+                                const float inv = __builtin_amdgcn_rcpf(range);
+                                const float t0 = __builtin_fmaf(mnY, inv, 1.0f), ninv = inv * -0.25f;
+                                float worst = 0.0f; // the block's largest |7 u - c|
 #pragma unroll
-                        for (int h = 16 / kA - 1; h >= 0; h--) { // groups of kA pixels: kA table reads in flight, bounded register use
-                                float D[kA];
-                                uint32_t g[kA];
+                                for (int i = 14; i >= 0; i -= 2) { // two pixels per step: one v_max3_f32 with abs modifiers
+                                        float dist[2];
 #pragma unroll
-                                for (int j = kA - 1; j >= 0; j--) {
-                                        g[j] = __float_as_uint(__builtin_fmaf(clamp01(__builtin_fmaf(Y[kA * h + j], ninv, t0)), 7.0f, kIndexBias));
-                                        D[j] = *(const float *) ((const char *) ta + (uint32_t) (g[j] << 8)); // rows of 64 floats
+                                        for (int h = 1; h >= 0; h--) {
+                                                const float u = clamp01(__builtin_fmaf(Y[i + h], ninv, t0));
+                                                const float r = __builtin_fmaf(u, 7.0f, kIndexBias); // the integer 2^23 + c
+                                                uint32_t &acc = i >= 10 ? hi : lo;
+                                                acc = (acc << 3) + __float_as_uint(r);
+                                                dist[h] = __builtin_fmaf(u, 7.0f, kIndexBias - r);   // 7 u - c
+                                        }
+                                        worst = fmaxf(fmaxf(worst, fabsf(dist[0])), fabsf(dist[1]));
                                 }
-                                __builtin_amdgcn_sched_barrier(0);
+                                const float eps = __builtin_fmaf(kAlphaEpsRange, inv, kAlphaEpsFixed);
+                                const lanemask_t certain = LANEMASK(worst < 0.5f - eps);
+                                if (__builtin_expect(certain == LANEMASK(true), 1)) { // __all, on the comparison's own lane mask
+                                        lo -= index_bias_sum(10, 3);
+                                        hi -= index_bias_sum(6, 3);
+                                        located = true;
+                                } else {
+                                        asm volatile("; alpha thresholds and comparisons" : "+v"(range), "+v"(mnY), "+v"(mxY) :: "memory");
+                                        count_exact_alpha();
+                                        lo = 0;
+                                        hi = 0;
+                                }
+                        }
+                }
+                if (!located) {
+                        const float inv7 = (float) (1.0 / 7.0);
+                        // (mxY - mnY) / 14.0f.  div14() is bit-identical to the division for x = 0 and for every x >= 2^-100 (exhaustive
+                        // device self-test); differences of byte-derived luma never fall in between, but the contract does not rest
+                        // on that: a wave that sees such a value takes the IEEE division.
+                        float mid = div14(range);
+                        if (__builtin_expect(__any((__float_as_uint(range) - 1u) < (kDiv14Exact - 1u)), 0)) {
+                                mid = range / 14.0f;
+                        }
+                        // ab[k] = 4 x the reference's threshold, bit for bit, for the comparisons with Y4.  The ends, range and mid stay
+                        // the reference's (so the range test, div14 and its route to the IEEE division are untouched: nothing here divides a
+                        // scaled value); the 4 goes into the multipliers, RN(4 (8 - k) mx) = 4 RN((8 - k) mx), of which one per threshold is
+                        // 4, 8 or 16 and rides in the fma of the sum; * inv7 scales with its operand, and + mid becomes fma(mid, 4, .).
+                        // ab[1] = RN(4 mn + 4 mid) takes the one multiplication this form adds.
+                        float ab[8];
+                        ab[1] = __builtin_fmaf(mid, 4.0f, mnY * 4.0f);
 #pragma unroll
-                                for (int j = kA - 1; j >= 0; j--) {
-                                        const int i = kA * h + j;
+                        for (int k = 2; k <= 7; k++) {
+                                const float cx_ = (float) (4 * (8 - k)), cn_ = (float) (4 * (k - 1));
+                                const float sum = k <= 3 || k == 5 ? __builtin_fmaf(mnY, cn_, cx_ * mxY) : __builtin_fmaf(mxY, cx_, cn_ * mnY);
+                                ab[k] = __builtin_fmaf(mid, 4.0f, sum * inv7);
+                        }
+
+                        // EmitAlphaIndicesYCoCgDXT5 (glsl:262-312): count c = #{k : a <= ab_k}, index = f(c).  Y[] holds Y4 and ab[] 4 x the thresholds
+                        // Thresholds in ascending order are T1..T7 = ab1, ab7, ab6, ab5, ab4, ab3, ab2 whenever they are
+                        // monotone (always, except degenerate blocks whose clamped min == max).  For a monotone set the
+                        // count is a 3-step binary search (3 compares + 4 selects instead of 7 compares + 7 adds); it is
+                        // the SAME function of (a, ab[]) as the reference's linear count, so results stay bit-identical.
+                        const float T1 = ab[1], T2 = ab[7], T3 = ab[6], T4 = ab[5], T5 = ab[4], T6 = ab[3], T7 = ab[2];
+                        // Monotone for sure when the clamped range exceeds 2^-10: consecutive thresholds are range/7 apart in exact
+                        // arithmetic and each carries < 2^-22 of rounding error (operands <= 7, results <= 1), so 2^-10/7 of spacing
+                        // cannot be overturned.  After the inset the range is >= 16/255/16 unless both ends clamp to the same bound,
+                        // so one compare decides for practically every block; only a wave that sees a narrower range evaluates the six
+                        // explicit comparisons.
+                        bool all_mono, all_wide = false; // both wave-uniform
+                        if (__builtin_expect(__all(range > 0.0009765625f), 1)) {
+                                all_mono = true;
+                                all_wide = true;
+                        } else {
+                                asm volatile("; explicit monotonicity check" ::: "memory");
+                                count_full_form(1);
+                                all_mono = __all((T1 <= T2) & (T2 <= T3) & (T3 <= T4) & (T4 <= T5) & (T5 <= T6) & (T6 <= T7));
+                        }
+                        // Fast form of the same count, valid under the wave-uniform range > 2^-10 test above.  The thresholds sit range/7
+                        // apart (+- 2^-21), so the position of a among them is known from ONE multiply-add up to the nearest threshold:
+                        //   t = 7 - (a - mnY) * 7/range (clamped to [0, 8)) puts threshold T(8-m) at t = m - 1/2  (m = 1..7, descending thresholds D_m = T(8-m));
+                        //   g = trunc(t) (saturating at 0): every D_m with m <= g lies >= 0.49 steps above a, every D_m with m >= g + 2 lies
+                        //   >= 0.49 steps below it (error of t < 6e-4 steps: rcp 1 ulp, mnY*inv rounded at magnitude <= 7168, fma rounding), so
+                        //   c = #{m : a <= D_m} = g + (a <= D_(g+1)) -- and THAT comparison is the reference's own, on the reference's own
+                        //   fp32 threshold (read back from the per-lane LDS column).  Row 7 = -inf serves g = 7 (a below every threshold).
+                        // 1 fma + cvt + address + compare + 2 integer ops per pixel instead of 3 compares + 4 selects + 3 carries.
+                        if (!kForceAlphaLinear && __builtin_expect(all_wide, 1)) {
+                                float *const ta = tab.alpha;
+                                ta[0 * 64] = T7; ta[1 * 64] = T6; ta[2 * 64] = T5; ta[3 * 64] = T4;
+                                ta[4 * 64] = T3; ta[5 * 64] = T2; ta[6 * 64] = T1; ta[7 * 64] = -__builtin_inff();
+                                // The same g without the conversion: u = (t - 1/2) / 7 = 6.5/7 - (a - mnY) / range with the clamp modifier (luma of
+                                // YUV sources can lie far outside [mnY, mxY]), then r = fma(u, 7, 2^23): r is the integer 2^23 + RN(7 u), so the low
+                                // bits of its pattern are g' = RN(clamp(t - 1/2, 0, 7)) = 0 .. 7.  g' = trunc(t) except where t is within its error
+                                // (< 6e-4 steps as above: rcp 1 ulp, mnY * inv rounded at magnitude <= 1024, two fma roundings) of an integer, or
+                                // exactly on it, where g' may be the neighbour of trunc(t).  There a lies 1/2 step from both nearest thresholds and
+                                // both rows give the same count: row g: g + (a <= D_(g+1)) = g + 1 (D_(g+1) is 1/2 step ABOVE a), row g + 1:
+                                // g + 1 + (a <= D_(g+2)) = g + 1 (D_(g+2) is 1/2 step BELOW a) -- the 0.49-step argument above covers either.
+                                // These fma are locating arithmetic only: no result of theirs is an operation of the reference.
+                                // The pattern kIndexBits + g' is used as it is: << 8 (the row offset) drops kIndexBits altogether, and the
+                                // index words collect it as a known sum that is subtracted once per word (the true words are 30 and 18 bits).
+                                const float inv = __builtin_amdgcn_rcpf(range);
+                                // t as above from the reference's ends; the pixels are Y4, so their factor takes the 1/4 (exact: the same t)
+                                const float t0 = __builtin_fmaf(mnY, inv, (float) (6.5 / 7.0)), ninv = inv * -0.25f;
+                                constexpr int kA = kDxt5AlphaGroup;
+#pragma unroll
+                                for (int h = 16 / kA - 1; h >= 0; h--) { // groups of kA pixels: kA table reads in flight, bounded register use
+                                        float D[kA];
+                                        uint32_t g[kA];
+#pragma unroll
+                                        for (int j = kA - 1; j >= 0; j--) {
+                                                g[j] = __float_as_uint(__builtin_fmaf(clamp01(__builtin_fmaf(Y[kA * h + j], ninv, t0)), 7.0f, kIndexBias));
+                                                D[j] = *(const float *) ((const char *) ta + (uint32_t) (g[j] << 8)); // rows of 64 floats
+                                        }
+                                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                                        for (int j = kA - 1; j >= 0; j--) {
+                                                const int i = kA * h + j;
+                                                uint32_t &acc = i >= 10 ? hi : lo;
+                                                acc = add_mask((acc << 3) + g[j], LANEMASK(Y[i] <= D[j]));
+                                        }
+                                        __builtin_amdgcn_sched_barrier(0);
+                                }
+                                lo -= index_bias_sum(10, 3);
+                                hi -= index_bias_sum(6, 3);
+                        } else if (!kForceAlphaLinear && __builtin_expect(all_mono, 1)) {
+#pragma unroll
+                                for (int i = 15; i >= 0; i--) {
+                                        const float a = Y[i];
+                                        const bool g4 = a <= T4;
+                                        const float t2 = g4 ? T2 : T6, t15 = g4 ? T1 : T5, t37 = g4 ? T3 : T7;
+                                        const bool g2 = a <= t2;
+                                        const float t1 = g2 ? t15 : t37;
+                                        const bool g1 = a <= t1;
                                         uint32_t &acc = i >= 10 ? hi : lo;
-                                        acc = add_mask((acc << 3) + g[j], LANEMASK(Y[i] <= D[j]));
+                                        acc = shift_in(acc, LANEMASK(g4));
+                                        acc = shift_in(acc, LANEMASK(g2));
+                                        acc = shift_in(acc, LANEMASK(g1));
                                 }
-                                __builtin_amdgcn_sched_barrier(0);
-                        }
-                        lo -= index_bias_sum(10, 3);
-                        hi -= index_bias_sum(6, 3);
-                } else if (!kForceAlphaLinear && __builtin_expect(all_mono, 1)) {
+                        } else { // reference form, 7 compares per pixel, for every lane of the wave (degenerate blocks only)
+                                // The empty asm keeps this a real branch: without it the compiler if-converts the two
+                                // sides and every block pays for both.
+                                asm volatile("; alpha linear fallback" ::: "memory");
 #pragma unroll
-                        for (int i = 15; i >= 0; i--) {
-                                const float a = Y[i];
-                                const bool g4 = a <= T4;
-                                const float t2 = g4 ? T2 : T6, t15 = g4 ? T1 : T5, t37 = g4 ? T3 : T7;
-                                const bool g2 = a <= t2;
-                                const float t1 = g2 ? t15 : t37;
-                                const bool g1 = a <= t1;
-                                uint32_t &acc = i >= 10 ? hi : lo;
-                                acc = shift_in(acc, LANEMASK(g4));
-                                acc = shift_in(acc, LANEMASK(g2));
-                                acc = shift_in(acc, LANEMASK(g1));
-                        }
-                } else { // reference form, 7 compares per pixel, for every lane of the wave (degenerate blocks only)
-                        // The empty asm keeps this a real branch: without it the compiler if-converts the two
-                        // sides and every block pays for both.
-                        asm volatile("; alpha linear fallback" ::: "memory");
+                                for (int i = 15; i >= 0; i--) {
+                                        const float a = Y[i];
+                                        uint32_t c = 0;
 #pragma unroll
-                        for (int i = 15; i >= 0; i--) {
-                                const float a = Y[i];
-                                uint32_t c = 0;
-#pragma unroll
-                                for (int k = 1; k <= 7; k++) {
-                                        c += (a <= ab[k]) ? 1u : 0u;
+                                        for (int k = 1; k <= 7; k++) {
+                                                c += (a <= ab[k]) ? 1u : 0u;
+                                        }
+                                        uint32_t &acc = i >= 10 ? hi : lo;
+                                        acc = (acc << 3) | c;
                                 }
-                                uint32_t &acc = i >= 10 ? hi : lo;
-                                acc = (acc << 3) | c;
                         }
                 }
                 // index = ((c + 1) & 7) ^ (((c + 1) & 7) < 2)   (glsl:281-290), i.e. 0->0, 1..6 -> c+1, 7->1,
@@ -1552,6 +1631,7 @@ extern "C" int ug_hip_dxt_encode_stats(unsigned long long full_form_waves[2], in
                 UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_cov_waves), zero, sizeof zero[0]));
                 static const unsigned long long no_pairs[kPairSlots * kPairSlotStride] = {};
                 UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_pair_waves), no_pairs, sizeof no_pairs));
+                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_alpha_waves), no_pairs, sizeof no_pairs));
         }
         return UG_HIP_SUCCESS;
 }
@@ -1570,6 +1650,22 @@ extern "C" int ug_hip_dxt_encode_stats_ex(unsigned long long *counts, int n, int
                 UG_HIP_TRY(hipMemcpyFromSymbol(pairs, HIP_SYMBOL(g_exact_pair_waves), sizeof pairs));
                 for (int i = 0; i < kPairSlots; i++) all[3] += pairs[i * kPairSlotStride];
                 for (int i = 0; i < n; i++) counts[i] = all[i];
+        }
+        return reset ? ug_hip_dxt_encode_stats(nullptr, 1) : UG_HIP_SUCCESS;
+}
+
+// The counter of the alpha stage's count from the location (4:2:2 sources -> DXT5-YCoCg): waves that held a block whose location
+// was not certified and went on to the thresholds and the reference's comparison.  An entry point of its own: counts[0 .. 3] above
+// keep their number and their meaning.  Either reset above clears this counter too.
+extern "C" int ug_hip_dxt_encode_stats_alpha(unsigned long long *exact_waves, int reset)
+{
+        UG_HIP_TRY(hipDeviceSynchronize());
+        if (exact_waves) {
+                static unsigned long long slots[kPairSlots * kPairSlotStride]; // (diagnostics, one caller at a time, as above)
+                UG_HIP_TRY(hipMemcpyFromSymbol(slots, HIP_SYMBOL(g_exact_alpha_waves), sizeof slots));
+                unsigned long long sum = 0;
+                for (int i = 0; i < kPairSlots; i++) sum += slots[i * kPairSlotStride];
+                *exact_waves = sum;
         }
         return reset ? ug_hip_dxt_encode_stats(nullptr, 1) : UG_HIP_SUCCESS;
 }
