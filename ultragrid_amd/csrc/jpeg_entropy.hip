@@ -243,10 +243,7 @@ __global__ __launch_bounds__(256) void entropy_wave_kernel(const int16_t *__rest
 constexpr int kWinWordsPerBlock = 16;
 
 // coefficients per skip group of the walks (a group that is zero in all 64 blocks of the wave costs one scalar branch)
-#ifndef UG_JPEG_WALK_GROUP
-#define UG_JPEG_WALK_GROUP 8 // 4 measures the same on 4K S2 content at q75 (23.7 vs 23.1 us)
-#endif
-constexpr int kWalkGroup = UG_JPEG_WALK_GROUP;
+constexpr int kWalkGroup = 8; // 4 measures the same on 4K S2 content at q75 (23.7 vs 23.1 us)
 
 // Per-lane bit accumulator of the emission walk.  Branch-free: a lane that appends nothing shifts in zero bits, and a lane whose
 // accumulator has not filled a word ORs 0 into its current window word -- every lane runs the same instructions.
@@ -366,9 +363,6 @@ __device__ __forceinline__ void walk_block(const uint32_t (&w)[32], const uint32
 // window, counted first and emitted again for the write-out (segment by segment, a wave each: count_pass / place / write_pass).  The stream is
 // byte-identical to the wave-per-segment coder + compaction.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef UG_JPEG_SKIP_POSITIONS
-#define UG_JPEG_SKIP_POSITIONS 1 // inside a group that is not empty, still skip the positions that are zero in all 64 blocks of the wave
-#endif
 constexpr int kPrivWords = 16;         // private string of a block: 512 bits (a 4K q75 frame needs ~80)
 constexpr int kPrivStride = 17;        // + one dump word for what does not fit; odd stride: the lanes' rows start in different banks
 
@@ -409,12 +403,11 @@ __device__ __forceinline__ void walk_group_private(const uint32_t (&w)[32], cons
         for (int k = g == 0 ? 1 : kWalkGroup * g; k < kWalkGroup * (g + 1); k++) {
                 const int v = coef_at(w, k);
                 const bool nz = v != 0;
-#if UG_JPEG_SKIP_POSITIONS
-                if (__ballot(nz) == 0) { // wave-uniform: this position is zero in all 64 blocks (two operations against ~20)
+                // inside a group that is not empty, still skip the positions that are zero in all 64 blocks of the wave
+                if (__ballot(nz) == 0) { // wave-uniform (two operations against ~20)
                         run16 += 16u;
                         continue;
                 }
-#endif
                 // T.81 F.1.2.1 without the absolute value: t = v (v >= 0) or v - 1 (v < 0) has |v|'s bit count in front of its sign run and
                 // its low `size` bits are the value bits; v_ffbh_i32 counts the sign run (-1 for t = 0: the saturating subtraction makes that size 0)
                 const int t = v + (v >> 31);
@@ -1637,12 +1630,25 @@ __global__ __launch_bounds__(256) void nori_place_kernel(const uint32_t *__restr
         }
 }
 
+bool env_is(const char *name, char value) { const char *const v = getenv(name); return v != nullptr && v[0] == value; }
+
+// The run-time switches: read from the environment here and nowhere else, once per encoder as it is created
+struct Switches {
+        bool force_wave_kernel = env_is("UG_JPEG_WAVE_KERNEL", '1'); // A/B switch back to the wave-per-segment coder + compaction (it remains the path for long restart intervals)
+        bool allow_fused = !env_is("UG_JPEG_FUSED", '0');            // =0: A/B switch, the front end always writes the coefficients to HBM
+        bool two_launch = !env_is("UG_JPEG_LOOKBACK", '1');          // =1 switches to the one-launch placement (decoupled look-back) for A/B
+        bool force_two_launch = env_is("UG_JPEG_LOOKBACK", '0');     // the two-launch placement for one-frame calls too (tests: every path with every input)
+        bool use_ticket = env_is("UG_JPEG_TICKET", '1');             // workgroup index = start-order ticket instead of blockIdx (or for good after a wait was given up)
+        bool flat_lookback = !env_is("UG_JPEG_FLAT", '0');           // one-frame calls: the flat form of the look-back (the default since round 5, profiles/r05_jpeg_one_frame.txt; =0: the windowed walk)
+        bool nori_off = env_is("UG_JPEG_NORI", '0');                 // long restart intervals and restart 0 on the old kernel (entropy_wave_kernel), for A/B
+        bool prof = env_is("UG_JPEG_PROF", '1');                     // the placing coder keeps phase clock sums (Encoder::prof)
+};
+
 struct Encoder {
+        Switches sw;
         int width, height, quality, ri, sub, hs, vs, ybl, mcu_w, mcu_h, n_mcu, n_seg, cap, device;
         int batch_cap; // frames the workspace below is sized for (1 after create; encode_batch grows it)
         int raw_cap;   // frames the buffers of the wave-per-segment path (scratch, seg_len, seg_ff, chunk totals) are sized for (0 until that path runs)
-        bool force_wave_kernel; // UG_JPEG_WAVE_KERNEL=1: A/B switch back to the wave-per-segment coder + compaction (it remains the path for long restart intervals)
-        bool allow_fused;       // UG_JPEG_FUSED=0: A/B switch, the front end always writes the coefficients to HBM
         std::vector<uint8_t> header;
         // device workspace
         float *div;
@@ -1657,11 +1663,7 @@ struct Encoder {
         uint8_t *slots;         // two-launch placement: a slot per workgroup of the coder (grown on demand), and the workgroups' byte counts
         size_t slots_cap;
         uint32_t *wg_bytes;
-        bool two_launch;        // UG_JPEG_LOOKBACK=1 switches to the one-launch placement (decoupled look-back) for A/B
-        bool force_two_launch;  // UG_JPEG_LOOKBACK=0: the two-launch placement for one-frame calls too (tests: every path with every input)
         unsigned long long *prof; // UG_JPEG_PROF=1: phase clock sums of the placing coder (device memory, kProfPhases + 1 words)
-        bool use_ticket;        // workgroup index = start-order ticket instead of blockIdx (UG_JPEG_TICKET=1, or for good after a wait was given up)
-        bool flat_lookback;     // one-frame calls: the flat form of the look-back (the default; UG_JPEG_FLAT=0 switches back to the windowed walk for A/B)
         uint8_t *header_dev;
         uint32_t *nori_bits, *nori_ff; // restart_interval 0, the parallel way: bit counts -> positions per block (+ the total); 0xFF bytes per 64-byte piece (+ the total)
         size_t nori_ff_cap;
@@ -1849,13 +1851,8 @@ void destroy(Encoder *e)
         delete e;
 }
 
-} // namespace
-
-extern "C" {
-
-typedef struct ug_hip_jpeg_encoder ug_hip_jpeg_encoder;
-
-int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restart_interval, int subsampling, int internal_cs, int flags, ug_hip_jpeg_encoder **out)
+// ---- ug_hip_jpeg_encoder_create_ex, stage by stage: refusals, options and scan geometry, headers, allocations ----
+int refuse_create(int width, int height, int restart_interval, int subsampling, int internal_cs, int flags, const void *out)
 {
         if (!out || width <= 0 || height <= 0 || width > 65535 || height > 65535 || restart_interval < 0 || restart_interval > 65535) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create: bad arguments");
@@ -1885,30 +1882,29 @@ int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restar
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create_ex: a 4:4:4:4 stream is R, G, B, alpha from RGBA input");
                 return UG_HIP_EUNSUPP;
         }
-        if (alpha) subsampling = 444; // the R, G, B stream of the same options, a fourth component behind
-        if (subsampling != 444 && !rgb_sub && ((flags & (UG_JPEG_NONINTERLEAVED | UG_JPEG_INPUT_UYVY)) || internal_cs == UG_JPEG_CS_RGB)) {
+        if (subsampling != 444 && !alpha && !rgb_sub && ((flags & (UG_JPEG_NONINTERLEAVED | UG_JPEG_INPUT_UYVY)) || internal_cs == UG_JPEG_CS_RGB)) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create_ex: a 4:2:x stream is Y'CbCr in one interleaved scan (R, G, B components, one scan per component, "
                                        "UG_JPEG_INPUT_UYVY: 4:4:4; R, G, B at 4:2:x: UG_JPEG_INPUT_RGB)");
                 return UG_HIP_EUNSUPP;
         }
-        Encoder *e = new Encoder();
-        e->alpha = alpha;
-        e->nc = alpha ? 3 : 2;
+        return UG_HIP_SUCCESS;
+}
+
+// what the stream is made of, and the blocks, MCUs and restart segments of its scans; refuses a segment too long for the coder's buffers
+int set_geometry(Encoder *e, int width, int height, int quality, int restart_interval, int subsampling, int internal_cs, int flags)
+{
+        e->alpha = subsampling == 4444;
+        if (e->alpha) subsampling = 444; // the R, G, B stream of the same options, a fourth component behind
+        e->nc = e->alpha ? 3 : 2;
         e->nonint = (flags & UG_JPEG_NONINTERLEAVED) != 0;
         e->in_uyvy = (flags & UG_JPEG_INPUT_UYVY) != 0;
+        e->rgb_sub = (flags & UG_JPEG_INPUT_RGB) != 0;
         e->cs_444 = internal_cs;
         e->ycc = subsampling == 444 && (internal_cs >= UG_JPEG_CS_YCBCR_BT601 || (e->in_uyvy && internal_cs == UG_JPEG_CS_ASIS));
         e->cs_rgb = e->ycc && !e->in_uyvy ? internal_cs : 0;
         e->cs_uyvy = subsampling != 444 && (internal_cs == UG_JPEG_CS_YCBCR_BT601 || internal_cs == UG_JPEG_CS_YCBCR_BT601_256LVLS) ? internal_cs : 0;
-        e->rgb_sub = rgb_sub;
-        e->ctab = (subsampling == 444 && !e->ycc) || rgb_sub ? 0 : 1;
+        e->ctab = (subsampling == 444 && !e->ycc) || e->rgb_sub ? 0 : 1;
         e->width = width; e->height = height; e->quality = quality;
-        e->force_wave_kernel = getenv("UG_JPEG_WAVE_KERNEL") != nullptr && getenv("UG_JPEG_WAVE_KERNEL")[0] == '1';
-        e->allow_fused = !(getenv("UG_JPEG_FUSED") != nullptr && getenv("UG_JPEG_FUSED")[0] == '0');
-        e->use_ticket = getenv("UG_JPEG_TICKET") != nullptr && getenv("UG_JPEG_TICKET")[0] == '1';
-        e->flat_lookback = !(getenv("UG_JPEG_FLAT") != nullptr && getenv("UG_JPEG_FLAT")[0] == '0'); // the default since round 5 (profiles/r05_jpeg_one_frame.txt)
-        e->two_launch = !(getenv("UG_JPEG_LOOKBACK") != nullptr && getenv("UG_JPEG_LOOKBACK")[0] == '1');
-        e->force_two_launch = getenv("UG_JPEG_LOOKBACK") != nullptr && getenv("UG_JPEG_LOOKBACK")[0] == '0';
         e->sub = subsampling;
         e->hs = subsampling == 444 ? 1 : 2; e->vs = subsampling == 420 ? 2 : 1; e->ybl = e->hs * e->vs;
         e->mcu_w = (width + 8 * e->hs - 1) / (8 * e->hs); e->mcu_h = (height + 8 * e->vs - 1) / (8 * e->vs); e->n_mcu = e->mcu_w * e->mcu_h;
@@ -1919,43 +1915,53 @@ int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restar
         // the blocks of every scan of a non-interleaved stream: component c's own ceil(x_c / 8) x ceil(y_c / 8) (T.81 A.2.2) -- the MCU grid, but for the
         // R scan of a 4:2:x R, G, B stream, which walks ceil(width / 8) x ceil(height / 8) blocks of its 2 mcu_w x vs mcu_h grid
         for (int c = 0; c < 4; c++) {
-                const bool sub0 = c == 0 && rgb_sub;
+                const bool sub0 = c == 0 && e->rgb_sub;
                 e->scan_bw[c] = sub0 ? (width + 7) / 8 : e->mcu_w;
                 e->scan_n[c] = sub0 ? e->scan_bw[c] * ((height + 7) / 8) : e->n_mcu;
                 e->scan_gw[c] = sub0 ? e->hs * e->mcu_w : e->mcu_w;
         }
         // one component per scan of a 4:2:x R, G, B stream: restart 0 = one segment of the largest scan's blocks; a segment holds ri blocks of one component
-        const bool nonint_sub = e->nonint && rgb_sub;
+        const bool nonint_sub = e->nonint && e->rgb_sub;
         if (nonint_sub && !restart_interval) e->ri = e->scan_n[0];
         const int seg_blocks = nonint_sub ? 1 : e->ybl + e->nc; // blocks per unit of the restart interval, at most
         if ((long) e->ri * seg_blocks * kRawBytesPerBlock + 8 > (1L << 30)) {
                 ug::set_last_error_msg("ug_hip_jpeg_encoder_create: picture too large for a scan without restart intervals");
-                delete e;
                 return UG_HIP_EUNSUPP;
         }
         e->n_seg = (e->n_mcu + e->ri - 1) / e->ri;
         for (int c = 0; c < 4; c++) e->scan_nseg[c] = (e->scan_n[c] + e->ri - 1) / e->ri;
         if (nonint_sub) e->n_seg = e->scan_nseg[0]; // (the largest scan: what the per-segment buffers are sized for)
         e->cap = e->ri * seg_blocks * kRawBytesPerBlock + 8; // unstuffed scan bytes of one segment (worst case 27 bits per coefficient)
+        return UG_HIP_SUCCESS;
+}
+
+// the stream's header(s) on the host, and the quantisers' divisors: [0, 64) component 0's, [64, 128) the others'
+void build_headers(Encoder *e, int restart_interval, float (&div)[128])
+{
         uint8_t ql[64], qc[64];
-        float div[128];
-        ug_hip_jpeg_qtable(quality, 0, ql);
-        ug_hip_jpeg_qtable(quality, 1, qc);
+        ug_hip_jpeg_qtable(e->quality, 0, ql);
+        ug_hip_jpeg_qtable(e->quality, 1, qc);
         ug_hip_jpeg_divisors(ql, div);
         ug_hip_jpeg_divisors(e->ctab == 0 ? ql : qc, div + 64); // R, G, B: every component is quantised with table 0
-        e->header = build_header(width, height, ql, qc, restart_interval, e->sub, e->ycc, -1, e->alpha, rgb_sub);
+        e->header = build_header(e->width, e->height, ql, qc, restart_interval, e->sub, e->ycc, -1, e->alpha, e->rgb_sub);
         if (e->nonint) {
-                for (int c = 0; c < 1 + e->nc; c++) e->scan_header[c] = build_header(width, height, ql, qc, restart_interval, e->sub, e->ycc, c, e->alpha, rgb_sub);
+                for (int c = 0; c < 1 + e->nc; c++) e->scan_header[c] = build_header(e->width, e->height, ql, qc, restart_interval, e->sub, e->ycc, c, e->alpha, e->rgb_sub);
                 e->header = e->scan_header[0]; // (what max_size and the capacity check count)
         }
+}
+
+// everything an encoder owns from its creation on (destroy() frees whatever part of it exists)
+hipError_t alloc_encoder(Encoder *e, const float (&div)[128])
+{
         hipError_t err = hipSuccess;
         auto alloc = [&](void **p, size_t n) { if (err == hipSuccess) err = hipMalloc(p, n); };
+        auto upload = [&](void *dst, const void *src, size_t n) { if (err == hipSuccess) err = hipMemcpy(dst, src, n, hipMemcpyHostToDevice); };
         alloc((void **) &e->div, sizeof div);
         if (err == hipSuccess) err = alloc_workspace(e, 1);
         alloc((void **) &e->header_dev, e->header.size());
         alloc((void **) &e->ticket, 64);
         if (err == hipSuccess) err = hipMemset(e->ticket, 0, 64);
-        if (getenv("UG_JPEG_PROF") != nullptr && getenv("UG_JPEG_PROF")[0] == '1') {
+        if (e->sw.prof) {
                 const size_t bytes = (size_t) kMaxBatch * e->n_mcu * (kProfPhases + 1) * 8; // a slot per workgroup of the largest launch
                 alloc((void **) &e->prof, bytes);
                 if (err == hipSuccess) err = hipMemset(e->prof, 0, bytes);
@@ -1966,11 +1972,469 @@ int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restar
         if (err == hipSuccess) memset(e->total_host, 0, kTotalBlocks * kTotalWords * 4);
         for (int c = 0; c < 1 + e->nc && e->nonint; c++) {
                 alloc((void **) &e->scan_header_dev[c], e->scan_header[c].size());
-                if (err == hipSuccess) err = hipMemcpy(e->scan_header_dev[c], e->scan_header[c].data(), e->scan_header[c].size(), hipMemcpyHostToDevice);
+                upload(e->scan_header_dev[c], e->scan_header[c].data(), e->scan_header[c].size());
         }
         if (err == hipSuccess) err = hipHostGetDevicePointer((void **) &e->total_host_dev, e->total_host, 0);
-        if (err == hipSuccess) err = hipMemcpy(e->div, div, sizeof div, hipMemcpyHostToDevice);
-        if (err == hipSuccess) err = hipMemcpy(e->header_dev, e->header.data(), e->header.size(), hipMemcpyHostToDevice);
+        upload(e->div, div, sizeof div);
+        upload(e->header_dev, e->header.data(), e->header.size());
+        return err;
+}
+
+// ---- ug_hip_jpeg_encoder_encode_batch, stage by stage ("the host side of a call") ----
+// The frames of a call as one stage sees them: the caller's up to stage_source(), the staged ones behind it -- never one under the other's name
+struct Source { ug_pixfmt_t in; const void *dev; int pitch /* 0: tightly packed */; size_t stride /* bytes between the frames of a batch */; };
+
+// Every refusal of a call, in front of its first device call.
+int refuse_call(const Encoder *e, const Source &src, int frames, const void *out_dev, size_t out_stride, size_t out_capacity, const size_t *out_len)
+{
+        if (!e || !src.dev || !out_dev || !out_len || (15 & (uintptr_t) out_dev) || frames < 1 || frames > kMaxBatch ||
+            (frames > 1 && ((out_stride & 15) || out_stride < out_capacity))) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: bad arguments (1..16 frames; out_stride a multiple of 16, >= out_capacity)");
+                return UG_HIP_EINVAL;
+        }
+        if (out_capacity < e->header.size() + 2) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: output buffer smaller than the JPEG header");
+                return UG_HIP_EINVAL;
+        }
+        // the source's pitch and alignment (ug_mi355x.h), here and not in the front ends: the fused kernels read the frame without one, and the
+        // answer must not depend on the path a restart interval or an alignment selects
+        const ug_pixfmt_t in = src.in;
+        const int line = in == UG_PF_UYVY ? ug::linesize(UG_PF_UYVY, e->width) : (in == UG_PF_RGBA ? 4 : 3) * e->width;
+        bool ok = true;
+        if (in == UG_PF_I420) {
+                ok = !src.pitch || src.pitch == e->width;
+        } else if (in == UG_PF_UYVY || in == UG_PF_RGBA) { // 32-bit words: lines (and the frames of a batch) start at multiples of 4
+                ok = (!src.pitch || (src.pitch >= line && !(src.pitch & 3))) && !(3 & (uintptr_t) src.dev) && (frames == 1 || !(src.stride & 3));
+        } else if (in == UG_PF_RGB) {
+                ok = !src.pitch || src.pitch >= line;
+        }
+        if (!ok) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: src_pitch must be 0 or at least the line size (I420: 0 or the width); UYVY and RGBA: "
+                                       "src_dev, src_pitch and src_stride multiples of 4");
+                return UG_HIP_EINVAL;
+        }
+        if (in == UG_PF_I420 && e->cs_uyvy) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: planar input is coded as it comes (no colour conversion)");
+                return UG_HIP_EUNSUPP;
+        }
+        if (e->alpha != (in == UG_PF_RGBA)) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:4:4:4 encoder takes RGBA, and only it takes RGBA");
+                return UG_HIP_EUNSUPP;
+        }
+        if (e->rgb_sub && in != UG_PF_RGB) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:2:x encoder created with UG_JPEG_INPUT_RGB takes RGB only");
+                return UG_HIP_EUNSUPP;
+        }
+        if (e->sub == 444 && !e->alpha && e->in_uyvy != (in == UG_PF_UYVY)) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:4:4 encoder takes RGB, or UYVY when created with UG_JPEG_INPUT_UYVY");
+                return UG_HIP_EUNSUPP;
+        }
+        const ug_pixfmt_t staged = e->sub == 444 && e->in_uyvy ? UG_PF_RGB : in; // (stage_source()); accepted: what run_front_end() has a branch for
+        if (!((staged == UG_PF_UYVY && e->sub != 444) || (staged == UG_PF_RGB && (e->rgb_sub || e->sub == 444)) || (staged == UG_PF_RGBA && e->alpha) ||
+              (staged == UG_PF_I420 && e->sub == 420))) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: input must be UYVY (4:2:0 / 4:2:2 encoder), I420 (4:2:0), RGB (4:4:4) or RGBA (4:4:4:4); "
+                                       "convert other formats with ug_hip_pixfmt_convert");
+                return UG_HIP_EUNSUPP;
+        }
+        return UG_HIP_SUCCESS;
+}
+
+// A device buffer that only grows: when its capacity is below `need`, freed and allocated again with `bytes` bytes for a capacity of `cap_new` (>= need)
+hipError_t grow(void **p, size_t *cap, size_t need, size_t cap_new, size_t bytes)
+{
+        if (*cap >= need) return hipSuccess;
+        if (*p) (void) hipFree(*p);
+        *p = nullptr; *cap = 0;
+        const hipError_t err = hipMalloc(p, bytes);
+        if (err == hipSuccess) *cap = cap_new;
+        return err;
+}
+
+// The caller's source -> the one every later stage reads: packed formats with their pitch filled in, and
+//  * the colour stage (create_ex's internal_cs): the frame(s) converted into cs_tmp, which then takes the input's place;
+//  * a 4:4:4 encoder fed UYVY (UG_JPEG_INPUT_UYVY): the frame(s) as 3 B/px in the coded colour space in cs_tmp, which then take the place of RGB input
+//    (never both: the colour stage of UYVY input is a 4:2:x encoder's, that of RGB input belongs to encoders without UG_JPEG_INPUT_UYVY)
+int stage_source(Encoder *e, Source s, int frames, ug_hip_stream_t stream, Source *staged)
+{
+        const int w = e->width, h = e->height;
+        if (!s.pitch && s.in != UG_PF_I420) s.pitch = s.in == UG_PF_UYVY ? ug::linesize(UG_PF_UYVY, w) : (s.in == UG_PF_RGBA ? 4 : 3) * w;
+        const int cs_to = s.in == UG_PF_RGB ? e->cs_rgb : (s.in == UG_PF_UYVY ? e->cs_uyvy : 0);
+        const bool to_444 = e->sub == 444 && e->in_uyvy;
+        if (cs_to || to_444) {
+                const int ls = to_444 || s.in == UG_PF_RGB ? 3 * w : ug::linesize(UG_PF_UYVY, w);
+                const size_t fb = ((size_t) ls * h + 15) / 16 * 16;
+                // (cs_tmp: for kMaxBatch frames at once -- a growing batch does not allocate again)
+                UG_HIP_TRY(grow((void **) &e->cs_tmp, &e->cs_tmp_bytes, fb * frames, fb * kMaxBatch, fb * kMaxBatch));
+                const int rc = to_444 ? ug::jpeg_uyvy_to_444(e->cs_444, s.dev, s.pitch, e->cs_tmp, ls, w, h, frames, s.stride, fb, stream)
+                            : ug::jpeg_colour_convert(s.in, s.in == UG_PF_RGB ? UG_JPEG_CS_RGB : UG_JPEG_CS_YCBCR_BT709, cs_to, s.dev, s.pitch, e->cs_tmp, ls, w, h, frames,
+                                                      s.stride, fb, stream);
+                if (rc != UG_HIP_SUCCESS) return rc;
+                s = { to_444 ? UG_PF_RGB : s.in, e->cs_tmp, ls, fb };
+        }
+        *staged = s;
+        return UG_HIP_SUCCESS;
+}
+
+// The path of a call: every decision, made in one place from the encoder, the staged source and the frame count (no device call, nothing written)
+struct PathChoice {
+        bool wave_path;    // segments too long for the block coder (or UG_JPEG_WAVE_KERNEL=1): the buffers of the wave-per-segment coder + compact_kernel
+        bool nori;         // ... a scan that is ONE segment, coded in parallel (code_without_restart)
+        bool seg_parallel; // ... several long segments, filled in parallel (fill_segments); neither: entropy_wave_kernel
+        bool fused_yuv, fused_rgb, fused_i420; // the block coder reads the frame itself (no front end)
+        bool two_launch;   // the block coder's placement: slots + gather launch, else the one-launch placement (look-back)
+        bool fused() const { return fused_yuv || fused_rgb || fused_i420; }
+};
+
+PathChoice choose_path(const Encoder *e, const Source &s, int frames)
+{
+        PathChoice pc = {};
+        const int w = e->width, h = e->height, S_frame = e->ri * (e->ybl + e->nc); // S_frame: blocks per (full) restart segment
+        pc.wave_path = (e->nonint ? e->ri : S_frame) > 256 || e->sw.force_wave_kernel; // (a scan of one component: a segment is ri blocks)
+        pc.nori = pc.wave_path && !e->sw.force_wave_kernel && e->n_seg == 1 && !e->sw.nori_off && (unsigned long long) e->cap * 8ull < (1ull << 32); // (UG_JPEG_WAVE_KERNEL=1: the old kernels throughout)
+        // Restart intervals too long for the block coder (more than 256 blocks per segment), SEVERAL segments: the same lane-per-block coding, into the per-segment buffers
+        // of the wave-per-segment coder (bit positions inside a segment by a segmented prefix sum), in front of that coder's compaction kernel -- which moves a segment
+        // per wave, where entropy_wave_kernel CODED a segment per wave, block after block (restart=2000 at 4K: 4 ms).  UG_JPEG_NORI=0: the old kernel.
+        // (which is faster, profiles/r06_encode_no_restart.txt: the old kernel takes ~0.9 us per block of a segment, the segments side by side; this way costs what the picture
+        // costs -- clearing the buffers, two passes over the blocks: ~0.58 ms at 4K -- whatever the interval.  4K: from ~650 blocks per segment, 1080p: from ~290)
+        pc.seg_parallel = pc.wave_path && !e->sw.force_wave_kernel && e->n_seg > 1 && !e->sw.nori_off &&
+                          0.9 * (double) e->ri * (e->nonint ? 1 : e->ybl + e->nc) > 150.0 + 5.2e-5 * (double) w * (double) h;
+        // Fused: forward DCT, quantiser, Huffman coding and byte stuffing in ONE kernel, a workgroup per 32 consecutive MCUs -- the quantised
+        // coefficients never reach HBM.  Needs whole segments per workgroup (32 % ri == 0) and the aligned geometry of the fast front end.
+        // a workgroup = 32 (RGB: 64) consecutive MCUs of the scan = whole segments: the restart interval must divide that.  fused_ok: the fused
+        // kernels divide MCU numbers by the MCUs of a row with a multiplication (CodeArgs::mcu_w_m32), exact while (n_mcu + 64) * mcu_w < 2^32
+        // and the row has more than one MCU -- every picture from 9 (17) pixels wide up to ~16K x 16K; others take the two-kernel path
+        const bool fused_ok = e->mcu_w > 1 && ((long) e->n_mcu + 64) * e->mcu_w < (1L << 32);
+        pc.fused_yuv = fused_ok && !pc.wave_path && e->sw.allow_fused && s.in == UG_PF_UYVY && e->sub != 444 && w % 16 == 0 && !(s.pitch & 15) && !(15 & (uintptr_t) s.dev) &&
+                       (frames == 1 || !(s.stride & 15)) && 32 % e->ri == 0;
+        // packed RGB (4:4:4, R, G, B components): any width and alignment (the edge blocks of the picture are loaded byte by byte)
+        pc.fused_rgb = fused_ok && !pc.wave_path && e->sw.allow_fused && s.in == UG_PF_RGB && e->sub == 444 && 64 % e->ri == 0 && !e->ycc && !e->nonint;
+        // planar I420: 8-byte row pieces of the three planes (width % 16 == 0 keeps the chroma rows 8-byte aligned too)
+        pc.fused_i420 = fused_ok && !pc.wave_path && e->sw.allow_fused && s.in == UG_PF_I420 && e->sub == 420 && w % 16 == 0 && (!s.pitch || s.pitch == w) && !(7 & (uintptr_t) s.dev) &&
+                        (frames == 1 || !(s.stride & 7)) && 32 % e->ri == 0;
+        // one frame per call: the look-back's waits are short (every workgroup of the frame is resident at once) and the second launch
+        // costs more than it saves (measured 39.4 against 41.3 us per 4K frame); from two frames up the two-launch placement wins.
+        // A scan of a non-interleaved stream goes on where the one before it ended: always the one-launch placement
+        pc.two_launch = !e->nonint && !pc.wave_path && e->sw.two_launch && (frames > 1 || e->sw.force_two_launch);
+        return pc;
+}
+
+// What the stages behind the path choice work on: the staged source, where the streams go, the path
+struct Call { Source src; int frames; uint8_t *out; size_t out_stride, out_capacity; hipStream_t st; BatchStride bs; PathChoice pc; };
+
+// The front end: the frames' quantised coefficients into cy / cb / cr (/ ca) -- or nothing, where the coder reads the frame itself (fused)
+int run_front_end(const Encoder *e, const Call &k)
+{
+        const Source &s = k.src; const BatchStride &bs = k.bs;
+        const int w = e->width, h = e->height, frames = k.frames;
+        const ug_hip_stream_t stream = (ug_hip_stream_t) k.st;
+        int rc = UG_HIP_SUCCESS;
+        if (k.pc.fused()) return rc;
+        if (s.in == UG_PF_UYVY) { // fused unpack + subsample + FDCT + quantise, grid.z = frame
+                return ug_hip_uyvy_to_jpeg42x_coeffs_batch(e->sub, s.dev, s.pitch, w, h, e->div, e->cy, e->cb, e->cr, frames, s.stride, (size_t) bs.coef_y * 2, (size_t) bs.coef_c * 2, stream);
+        }
+        if (s.in == UG_PF_RGB && e->rgb_sub) { // R, G, B at 4:2:x: R over its full grid, G and B box-averaged, in one pass over the frame(s) (rgb_jpeg42x_kernel)
+                return ug::jpeg_fdct_quant_rgb42x(e->sub, s.dev, s.pitch, w, h, e->div, e->cy, e->cb, e->cr, frames, s.stride, (size_t) bs.coef_y * 2, (size_t) bs.coef_c * 2, stream);
+        }
+        for (int f = 0; f < frames && rc == UG_HIP_SUCCESS; f++) {
+                const uint8_t *const fr = (const uint8_t *) s.dev + f * s.stride;
+                int16_t *const cy = e->cy + f * bs.coef_y, *const cb = e->cb + f * bs.coef_c, *const cr = e->cr + f * bs.coef_c;
+                if (s.in == UG_PF_RGB && e->ycc) { // Y', Cb, Cr (the colour stage's output): the luma quantiser for component 0, the chroma one for the others
+                        rc = ug::jpeg_fdct_quant_strided(fr, s.pitch, 3, w, h, e->mcu_w, e->mcu_h, e->div, cy, nullptr, stream);
+                        if (rc == UG_HIP_SUCCESS) rc = ug::jpeg_fdct_quant_strided(fr + 1, s.pitch, 3, w, h, e->mcu_w, e->mcu_h, e->div + 64, cb, nullptr, stream);
+                        if (rc == UG_HIP_SUCCESS) rc = ug::jpeg_fdct_quant_strided(fr + 2, s.pitch, 3, w, h, e->mcu_w, e->mcu_h, e->div + 64, cr, nullptr, stream);
+                } else if (s.in == UG_PF_RGB) { // GPUJPEG_444_U8_P012, components kept as R, G, B (gpujpeg.cpp:303-305,336)
+                        rc = ug::jpeg_fdct_quant_rgb444(fr, s.pitch, w, h, e->mcu_w, e->mcu_h, e->div, cy, cb, cr, stream);
+                } else if (s.in == UG_PF_RGBA) { // GPUJPEG_4444_U8_P0123: R, G, B, A in one pass over the frame (rgba_jpeg4444_kernel)
+                        rc = ug::jpeg_fdct_quant_rgba4444(fr, s.pitch, w, h, e->mcu_w, e->mcu_h, e->div, cy, cb, cr, e->ca + f * bs.coef_c, stream);
+                } else { // I420, planar passthrough (GPUJPEG_420_U8_P0P1P2, gpujpeg.cpp:335): Y, U, V planes back to back, tightly packed
+                        const int cw = (w + 1) / 2, ch = (h + 1) / 2;
+                        const uint8_t *const u = fr + (size_t) w * h, *const v = u + (size_t) cw * ch;
+                        rc = ug::jpeg_fdct_quant_strided(fr, w, 1, w, h, 2 * e->mcu_w, 2 * e->mcu_h, e->div, cy, nullptr, stream);
+                        if (rc == UG_HIP_SUCCESS) rc = ug::jpeg_fdct_quant_strided(u, cw, 1, cw, ch, e->mcu_w, e->mcu_h, e->div + 64, cb, nullptr, stream);
+                        if (rc == UG_HIP_SUCCESS) rc = ug::jpeg_fdct_quant_strided(v, cw, 1, cw, ch, e->mcu_w, e->mcu_h, e->div + 64, cr, nullptr, stream);
+                }
+        }
+        return rc;
+}
+
+// One scan as the coders take it: the frame's one interleaved scan, or one scan of a non-interleaved stream -- a single component's blocks (its MCU is one
+// block), its own header bytes, and the stream goes on where the scan before it ended
+struct ScanPlan {
+        const int16_t *coef; int tab0; const uint8_t *header; int header_len; const uint32_t *base; uint32_t *total;
+        int bw, n, gw, n_seg; // the scan's MCUs: bw x (n / bw), component 0's blocks in a grid gw blocks wide, in n_seg segments (Encoder::scan_* for one component)
+        long stride;          // int16 elements between the frames' planes of component 0
+        int hs, vs, nc;       // component 0's blocks in an MCU, and the components behind it (one component: 1, 1, 0)
+        int per_mcu() const { return hs * vs + nc; }
+};
+
+// scan c of a non-interleaved stream (scan 0: SOI .. SOS in front, scans 1, 2 (, 3): their SOS); c < 0: the interleaved scan
+ScanPlan scan_plan(const Encoder *e, const BatchStride &bs, int c)
+{
+        if (c < 0) return { e->cy, 0, e->header_dev, (int) e->header.size(), nullptr, e->total_host_dev, e->mcu_w, e->n_mcu, e->hs * e->mcu_w, e->n_seg, bs.coef_y, e->hs, e->vs, e->nc };
+        const int16_t *const planes[4] = { e->cy, e->cb, e->cr, e->ca };
+        return { planes[c], e->ycc && c > 0 ? 1 : 0, e->scan_header_dev[c], (int) e->scan_header[c].size(), c > 0 ? e->total_host_dev + c * kTotalWords : nullptr,
+                 e->total_host_dev + (c + 1) * kTotalWords, e->scan_bw[c], e->scan_n[c], e->scan_gw[c], e->scan_nseg[c], c > 0 ? bs.coef_c : bs.coef_y, 1, 1, 0 };
+}
+
+// the block-parallel coder, fused or behind the front end; two_launch: slots + gather launch, else the one-launch placement (look-back)
+int launch_coder(Encoder *e, const Call &k, const ScanPlan &p, bool two_launch)
+{
+        const hipStream_t st = k.st;
+        const int frames = k.frames, S = e->ri * p.per_mcu(); // blocks per (full) restart segment
+        const bool fused = p.nc != 0 && k.pc.fused(); // (a scan of one component reads coefficients)
+        if (++e->gen >= (1u << 30)) { // the status words carry the call's generation in 30 bits: start over on clean words
+                UG_HIP_TRY(hipMemsetAsync(e->status, 0, (size_t) e->n_mcu * 8 * e->batch_cap, st));
+                e->gen = 1;
+        }
+        CodeArgs a = {};
+        a.mcu_w = p.bw; a.n_mcu = p.n; a.hs = p.hs; a.vs = p.vs; a.ctab = e->ctab; a.ri = e->ri; a.n_seg = p.n_seg; a.S = S;
+        a.gw0 = p.gw; a.nc = p.nc; a.tab0 = p.tab0;
+        a.cy = p.coef; a.cb = e->cb; a.cr = e->cr; a.ca = e->ca; a.coef_y = p.stride; a.coef_c = k.bs.coef_c;
+        a.src = (const uint8_t *) k.src.dev; a.pitch = k.src.pitch; a.width = e->width; a.height = e->height; a.src_stride = k.src.stride;
+        a.out = k.out; a.out_stride = k.out_stride; a.capacity = k.out_capacity; a.header = p.header; a.header_len = p.header_len; a.base = p.base; a.total_pinned = p.total;
+        a.status = e->status; a.n_status = e->n_mcu; a.gen = e->gen; a.ticket = e->sw.use_ticket ? e->ticket : nullptr; a.prof = e->prof;
+        // divisions by S, blocks per MCU and MCUs per row as multiplications, where the ranges allow (CodeArgs)
+        auto m16 = [](int d) { return (uint32_t) (65536 / d + 1); };
+        auto m32 = [](long d) { return d > 1 ? (uint32_t) ((1ull << 32) / (unsigned long long) d + 1ull) : 0u; };
+        a.S_m16 = m16(S);                 // x < 256 lanes, S <= 256: x * S < 2^16
+        a.per_mcu_m16 = m16(p.per_mcu()); // x < S <= 256, per_mcu <= 6
+        a.S_m32 = m32(S);                 // x <= S * 16 window words + S
+        a.mcu_w_m32 = m32(e->mcu_w);      // x < n_mcu + 64 (the lanes of a last, short workgroup): see fused_ok
+        int waves, kwin = 16;
+        if (fused) {
+                const int mcus = k.pc.fused_rgb ? 64 : 32; // MCUs per workgroup
+                a.n_wg = (e->n_mcu + mcus - 1) / mcus;
+                a.G = mcus / e->ri;
+                waves = e->sub == 422 ? 2 : 3;
+                if (e->sub != 422) kwin = 12;
+        } else {
+                // waves per workgroup: the count that leaves the fewest lanes idle (fewer waves on a tie)
+                waves = 1;
+                for (int n = 1; n <= 4; n++) {
+                        if (64 * n >= S && (64 * n / S) * S * (64 * waves) > (64 * waves / S) * S * (64 * n)) waves = n;
+                        if (64 * waves < S) waves = n;
+                }
+                // (the kernel's per-segment LDS words are sized for segments of at least 3 blocks, kMaxSeg = lanes / 3 + 1: the shortest ones an
+                // interleaved scan has; a one-component scan with restart interval 1 or 2 has shorter ones and leaves lanes idle instead)
+                a.G = std::min(64 * waves / S, 64 * waves / 3);
+                a.n_wg = (a.n_seg + a.G - 1) / a.G;
+        }
+        if (a.n_wg > e->n_mcu) { // (the look-back's status words and the workgroups' byte counts: n_mcu per frame; a workgroup codes at least 21 blocks)
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: more coder workgroups than status words");
+                return UG_HIP_ERUNTIME;
+        }
+        if (two_launch) {
+                // a slot holds whatever the one-pass path can produce: every window full, every byte stuffed, the markers (+ the padding the
+                // gather's word reads may touch); a workgroup on the general path that needs more reports it and the call runs again, one launch
+                a.slot_bytes = ((size_t) 64 * waves * kwin * 4 * 2 + 2 * (size_t) a.G + 16 + 255) / 256 * 256;
+                const size_t need = a.slot_bytes * (size_t) a.n_wg * (size_t) frames;
+                const size_t want = a.slot_bytes * (size_t) a.n_wg * (size_t) e->batch_cap;
+                // + 8: the gather reads the stream in 8-byte words and may touch up to 7 bytes past byte n of a slot; a general-path workgroup
+                // may fill its slot to the last byte, and the last slot of the last frame ends where the allocation would
+                if (grow((void **) &e->slots, &e->slots_cap, need, want, want + 8) != hipSuccess) {
+                        (void) hipGetLastError();
+                        two_launch = false; // no room for the slots: the one-launch placement needs none
+                }
+        }
+        if (two_launch) { a.slots = e->slots; a.wg_bytes = e->wg_bytes; }
+        // The flat look-back reads n_wg^2 / 2 eight-byte words per frame: 4 MB at 4K (n_wg ~ 1000) -- all L2 hits, 10 % off the one-frame call --,
+        // 64 MB at 8K (-6 %), and it grows with the square: past kFlatMaxWg workgroups a frame the windowed walk (16 round trips per 1024
+        // workgroups) is the cheaper form again (nothing bounded it for the sizes create() accepts, up to 65535 x 65535)
+        constexpr int kFlatMaxWg = 4096;
+        a.flat = frames == 1 && e->sw.flat_lookback && a.n_wg <= kFlatMaxWg ? 1 : 0;
+        const dim3 grid((unsigned) a.n_wg, (unsigned) frames);
+        if (fused) {
+                if (k.pc.fused_i420) hipLaunchKernelGGL((jpeg_code_kernel<3, 1420>), grid, dim3(192), 0, st, a, (const float *) e->div);
+                else if (e->sub == 420) hipLaunchKernelGGL((jpeg_code_kernel<3, 420>), grid, dim3(192), 0, st, a, (const float *) e->div);
+                else if (e->sub == 422 && frames >= 2) hipLaunchKernelGGL((jpeg_code_kernel<2, 422, true>), grid, dim3(128), 0, st, a, (const float *) e->div);
+                else if (e->sub == 422) hipLaunchKernelGGL((jpeg_code_kernel<2, 422>), grid, dim3(128), 0, st, a, (const float *) e->div);
+                else hipLaunchKernelGGL((jpeg_code_kernel<3, 444>), grid, dim3(192), 0, st, a, (const float *) e->div);
+        } else {
+                switch (waves) {
+                case 1: hipLaunchKernelGGL((jpeg_code_kernel<1, 0>), grid, dim3(64), 0, st, a, (const float *) e->div); break;
+                case 2: hipLaunchKernelGGL((jpeg_code_kernel<2, 0>), grid, dim3(128), 0, st, a, (const float *) e->div); break;
+                case 3: hipLaunchKernelGGL((jpeg_code_kernel<3, 0>), grid, dim3(192), 0, st, a, (const float *) e->div); break;
+                default: hipLaunchKernelGGL((jpeg_code_kernel<4, 0>), grid, dim3(256), 0, st, a, (const float *) e->div); break;
+                }
+        }
+        if (two_launch) {
+                hipLaunchKernelGGL(jpeg_gather_kernel, dim3((unsigned) ((a.n_wg + 3) / 4), (unsigned) frames), dim3(256), 0, st, (const uint8_t *) e->slots, a.slot_bytes,
+                                   (const uint32_t *) e->wg_bytes, a.n_wg, k.out, k.out_stride, k.out_capacity, p.header, p.header_len, p.total);
+        }
+        return UG_HIP_SUCCESS;
+}
+
+// frame f of scan p as the lane-per-block kernels (nori_*) take it; ri: MCUs per restart interval
+NoriScan nori_scan(const Encoder *e, const Call &k, const ScanPlan &p, int f, int ri)
+{
+        NoriScan s = {};
+        s.c0 = p.coef + f * p.stride; s.c1 = e->cb + f * k.bs.coef_c; s.c2 = e->cr + f * k.bs.coef_c; s.c3 = e->ca ? e->ca + f * k.bs.coef_c : nullptr;
+        s.mcu_w = p.bw; s.n_mcu = p.n; s.hs = p.hs; s.vs = p.vs; s.nc = p.nc; s.tab0 = p.tab0; s.ctab = e->ctab; s.ri = ri; s.gw0 = p.gw;
+        return s;
+}
+
+// A scan that is ONE segment (restart_interval 0), coded in parallel (nori_*_kernel above); frame after frame on the stream, one more host synchronisation per frame
+// (the scan's length in bits, to size the byte-stuffing launches).
+int code_without_restart(Encoder *e, const Call &k, const ScanPlan &p)
+{
+        const hipStream_t st = k.st;
+        const uint32_t n_blocks = (uint32_t) p.n * (uint32_t) p.per_mcu();
+        // (a bit count per block of the largest scan + the total: the R scan of a 4:2:x R, G, B stream has at most ybl * n_mcu blocks)
+        if (!e->nori_bits) UG_HIP_TRY(hipMalloc((void **) &e->nori_bits, ((size_t) e->n_mcu * (e->ybl + e->nc) + 1) * 4));
+        for (int f = 0; f < k.frames; f++) {
+                const NoriScan s = nori_scan(e, k, p, f, p.n);
+                hipLaunchKernelGGL(nori_len_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, e->nori_bits);
+                hipLaunchKernelGGL(nori_scan_kernel, dim3(1), dim3(1024), 0, st, e->nori_bits, n_blocks);
+                uint32_t *const bits_host = e->total_host + kOddBlock * kTotalWords; // (a word of the pinned block of its own)
+                UG_HIP_TRY(hipMemcpyAsync(bits_host, e->nori_bits + n_blocks, 4, hipMemcpyDeviceToHost, st));
+                UG_HIP_TRY(hipStreamSynchronize(st));
+                const size_t bytes = ((size_t) *bits_host + 7) / 8;
+                const uint32_t n_pieces = (uint32_t) ((bytes + 63) / 64);
+                UG_HIP_TRY(grow((void **) &e->nori_ff, &e->nori_ff_cap, (size_t) n_pieces + 1, ((size_t) n_pieces + 1) * 2, ((size_t) n_pieces + 1) * 4 * 2));
+                UG_HIP_TRY(hipMemsetAsync(e->scratch, 0, (bytes + 8 + 3) & ~(size_t) 3, st));
+                hipLaunchKernelGGL(nori_emit_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, (const uint32_t *) e->nori_bits, e->scratch, n_blocks, 0u);
+                if (n_pieces) hipLaunchKernelGGL(nori_ff_kernel, dim3((n_pieces + 255) / 256), dim3(256), 0, st, (const uint32_t *) e->scratch, (const uint32_t *) e->nori_bits + n_blocks, n_pieces, e->nori_ff);
+                hipLaunchKernelGGL(nori_scan_kernel, dim3(1), dim3(1024), 0, st, e->nori_ff, n_pieces);
+                hipLaunchKernelGGL(nori_place_kernel, dim3(n_pieces ? (n_pieces + 255) / 256 : 1), dim3(256), 0, st, (const uint32_t *) e->scratch, (const uint32_t *) e->nori_bits + n_blocks,
+                                   n_pieces, (const uint32_t *) e->nori_ff, k.out + (size_t) f * k.out_stride, p.header, p.header_len, k.out_capacity, p.total, p.base, f);
+        }
+        return UG_HIP_SUCCESS;
+}
+
+// Several segments too long for the block coder, filled in parallel (PathChoice::seg_parallel, and choose_path() on when): what entropy_wave_kernel leaves
+// for compact_kernel -- the unstuffed segments, their lengths, 0xFF counts and chunk totals
+int fill_segments(Encoder *e, const Call &k, const ScanPlan &p)
+{
+        const hipStream_t st = k.st;
+        const uint32_t per_mcu = (uint32_t) p.per_mcu(), n_blocks = (uint32_t) p.n * per_mcu;
+        if (!e->nori_bits) UG_HIP_TRY(hipMalloc((void **) &e->nori_bits, ((size_t) e->n_mcu * (e->ybl + e->nc) + 1) * 4));
+        UG_HIP_TRY(grow((void **) &e->nori_ff, &e->nori_ff_cap, (size_t) e->n_seg + 1, (size_t) e->n_seg + 1, ((size_t) e->n_seg + 1) * 4));
+        for (int f = 0; f < k.frames; f++) {
+                const NoriScan s = nori_scan(e, k, p, f, e->ri);
+                uint32_t *const raw = e->scratch + (size_t) f * k.bs.raw_words;
+                hipLaunchKernelGGL(nori_len_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, e->nori_bits);
+                hipLaunchKernelGGL(nori_segscan_kernel, dim3(1), dim3(1024), 0, st, e->nori_bits, n_blocks, (uint32_t) e->ri * per_mcu, e->nori_ff);
+                UG_HIP_TRY(hipMemsetAsync(raw, 0, (size_t) p.n_seg * (size_t) e->cap, st));
+                hipLaunchKernelGGL(nori_emit_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, (const uint32_t *) e->nori_bits, raw, (uint32_t) e->ri * per_mcu,
+                                   (uint32_t) (e->cap / 4));
+                hipLaunchKernelGGL(nori_segstat_kernel, dim3((p.n_seg + 3) / 4), dim3(256), 0, st, (const uint32_t *) raw, (uint32_t) (e->cap / 4), (const uint32_t *) e->nori_ff, p.n_seg,
+                                   e->seg_len + (size_t) f * k.bs.seg, e->seg_ff + (size_t) f * k.bs.seg, e->chunk_tot + (size_t) f * k.bs.tot_words);
+        }
+        return UG_HIP_SUCCESS;
+}
+
+// One scan of every frame onto the stream, by the coder the path choice names
+int code_scan(Encoder *e, const Call &k, const ScanPlan &p)
+{
+        if (!k.pc.wave_path) return launch_coder(e, k, p, k.pc.two_launch);
+        if (k.pc.nori) return code_without_restart(e, k, p);
+        // restart intervals of more than 256 blocks: the segments unstuffed into their buffers, then the compaction.  The totals this call's coder adds into
+        // start from zero (a smaller batch in between must not leave stale slices behind)
+        UG_HIP_TRY(hipMemsetAsync(e->chunk_tot, 0, (size_t) k.bs.tot_words * 4 * k.frames, k.st));
+        BatchStride bsc = k.bs; // (the frames' planes of this scan's component 0)
+        bsc.coef_y = p.stride;
+        if (k.pc.seg_parallel) {
+                const int rc = fill_segments(e, k, p);
+                if (rc != UG_HIP_SUCCESS) return rc;
+        } else { // (the planes behind component 0, and their table: left as the two callers of old passed them -- a scan of one component reads neither)
+                const bool one = p.nc == 0;
+                hipLaunchKernelGGL(entropy_wave_kernel, dim3((p.n_seg + 3) / 4, k.frames), dim3(256), 0, k.st, p.coef, one ? p.coef : e->cb, one ? p.coef : e->cr,
+                                   one ? p.coef : (e->ca ? e->ca : e->cr), p.bw, p.n, p.hs, p.vs, p.gw, one ? 0 : e->ctab, p.nc, p.tab0, e->ri, p.n_seg, e->scratch, e->cap / 4,
+                                   e->seg_len, e->seg_ff, e->chunk_tot, bsc);
+        }
+        hipLaunchKernelGGL(compact_kernel, dim3((p.n_seg + 3) / 4, k.frames), dim3(256), 0, k.st, (const uint8_t *) e->scratch, e->cap, e->seg_len, e->seg_ff, e->chunk_tot,
+                           p.n_seg, k.out, p.header, p.header_len, k.out_capacity, p.total, p.base, bsc);
+        return UG_HIP_SUCCESS;
+}
+
+// The coding stage: every scan of the call's streams queued, from the staged source or the front end's coefficients.
+// Non-interleaved: one scan per component (T.81 A.2.2; the reference's default for RGB input, gpujpeg.cpp:303).  Each scan is a coder over ONE
+// component's coefficients -- DC prediction and restart intervals (in blocks) of its own, its markers numbered from RST0 -- preceded by
+// its header bytes.  Where a scan ends is only known once it is coded: the launch of scan c reads the length scan c - 1 left behind
+// (CodeArgs::base) and goes on from there, over the EOI every coded stream ends with.  Scan after scan on the stream, no intermediate buffer.
+int code_streams(Encoder *e, const Call &k)
+{
+        const int n_scans = e->nonint ? 1 + e->nc : 1;
+        memset(e->total_host, 0, (size_t) (e->nonint ? 1 + n_scans : 1) * kTotalWords * 4); // the call's pinned words: block 0, and a block per scan of a non-interleaved stream
+        if (k.pc.wave_path && k.frames > e->raw_cap) {
+                const hipError_t err = alloc_raw(e, e->batch_cap);
+                if (err != hipSuccess) {
+                        ug::set_last_error(err, "ug_hip_jpeg_encoder_encode: work buffers of the wave-per-segment coder");
+                        free_raw(e);
+                        return UG_HIP_ERUNTIME;
+                }
+        }
+        for (int c = 0; c < n_scans; c++) {
+                const int rc = code_scan(e, k, scan_plan(e, k.bs, e->nonint ? c : -1));
+                if (rc != UG_HIP_SUCCESS) return rc;
+        }
+        UG_HIP_LAUNCH_CHECK();
+        return UG_HIP_SUCCESS;
+}
+
+// Collecting the result: the call's one synchronisation, the lengths, and the two things a coder can report instead of a stream.
+int collect_streams(Encoder *e, const Call &k, size_t *out_len)
+{
+        const int first = e->nonint ? 1 : 0, last = e->nonint ? 1 + e->nc : 0; // the blocks of total_host the call's scans report into; the last one: the streams' lengths
+        for (;;) {
+                UG_HIP_TRY(hipStreamSynchronize(k.st)); // ONE synchronisation for the batch
+                if (!e->nonint && !k.pc.wave_path && e->total_host[kMaxBatch + 1] != 0) { // a workgroup's bytes did not fit its slot (near-lossless quality on noise): once more, in one launch
+                        e->total_host[kMaxBatch + 1] = 0;
+                        const int rc = launch_coder(e, k, scan_plan(e, k.bs, -1), false);
+                        if (rc != UG_HIP_SUCCESS) return rc;
+                        UG_HIP_LAUNCH_CHECK();
+                        UG_HIP_TRY(hipStreamSynchronize(k.st));
+                }
+                uint32_t gave_up = 0;
+                for (int b = first; b <= last; b++) gave_up |= e->total_host[b * kTotalWords + kMaxBatch];
+                if (!gave_up) break;
+                (void) hipMemset(e->ticket, 0, 4); // a workgroup gave up waiting for an earlier one: reported, never waited out
+                if (e->sw.use_ticket) {
+                        ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: the stream placement gave up waiting for an earlier workgroup");
+                        return UG_HIP_ERUNTIME;
+                }
+                // the start order was not the index order after all: from now on the index IS the start order.  Said once, loudly: the call that met it cost a
+                // spin-out (the waiting waves gave up after kSpinLimit polls), and every later call of this encoder takes the ticket form (measured ~8 % of the
+                // coder kernel); UG_JPEG_TICKET=1 starts that way.  Coded again from where the first attempt was: the staged source, the front end's coefficients
+                e->sw.use_ticket = true;
+                fprintf(stderr, "[ug_mi355x] JPEG encoder %dx%d: a workgroup of the one-launch stream placement waited for a predecessor that had not been "
+                                "dispatched (workgroups did not start in index order); this call is encoded again and the encoder uses start-order tickets "
+                                "from now on (UG_JPEG_TICKET=1 selects that from the start)\n", e->width, e->height);
+                const int rc = code_streams(e, k);
+                if (rc != UG_HIP_SUCCESS) return rc;
+        }
+        bool fits = true;
+        for (int f = 0; f < k.frames; f++) {
+                out_len[f] = e->total_host[last * kTotalWords + f]; // (what the stream needs, when it does not fit: nothing past the capacity was written)
+                fits = fits && out_len[f] <= k.out_capacity;
+        }
+        if (!fits && k.frames == 1) {
+                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: stream does not fit the output buffer (out_len = needed size)");
+                return UG_HIP_EINVAL;
+        }
+        // a batch reports per frame: out_len[f] > out_capacity = that stream did not fit (the others are complete)
+        return UG_HIP_SUCCESS;
+}
+
+} // namespace
+
+extern "C" {
+
+typedef struct ug_hip_jpeg_encoder ug_hip_jpeg_encoder;
+
+int ug_hip_jpeg_encoder_create_ex(int width, int height, int quality, int restart_interval, int subsampling, int internal_cs, int flags, ug_hip_jpeg_encoder **out)
+{
+        int rc = refuse_create(width, height, restart_interval, subsampling, internal_cs, flags, out);
+        if (rc != UG_HIP_SUCCESS) return rc;
+        Encoder *e = new Encoder();
+        rc = set_geometry(e, width, height, quality, restart_interval, subsampling, internal_cs, flags);
+        if (rc != UG_HIP_SUCCESS) {
+                delete e;
+                return rc;
+        }
+        float div[128];
+        build_headers(e, restart_interval, div);
+        const hipError_t err = alloc_encoder(e, div);
         if (err != hipSuccess) {
                 ug::set_last_error(err, "ug_hip_jpeg_encoder_create");
                 destroy(e);
@@ -2010,38 +2474,14 @@ int ug_hip_jpeg_encoder_encode(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, const v
         return ug_hip_jpeg_encoder_encode_batch(enc, in, 1, src_dev, src_pitch, 0, out_dev, 0, out_capacity, out_len, stream);
 }
 
+// The stages of a call in order: refusals, work buffers, staged source, path choice, front end, coding, collecting the result
 int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, int frames, const void *src_dev, int src_pitch, size_t src_stride,
                                      void *out_dev, size_t out_stride, size_t out_capacity, size_t *out_len, ug_hip_stream_t stream)
 {
         Encoder *e = (Encoder *) enc;
-        if (!e || !src_dev || !out_dev || !out_len || (15 & (uintptr_t) out_dev) || frames < 1 || frames > kMaxBatch ||
-            (frames > 1 && ((out_stride & 15) || out_stride < out_capacity))) {
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: bad arguments (1..16 frames; out_stride a multiple of 16, >= out_capacity)");
-                return UG_HIP_EINVAL;
-        }
-        if (out_capacity < e->header.size() + 2) {
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: output buffer smaller than the JPEG header");
-                return UG_HIP_EINVAL;
-        }
-        // the source's pitch and alignment (ug_mi355x.h), here and not in the front ends: the fused kernels read the frame without one, and the
-        // answer must not depend on the path a restart interval or an alignment selects
-        {
-                const int line = in == UG_PF_UYVY ? ug::linesize(UG_PF_UYVY, e->width) : (in == UG_PF_RGBA ? 4 : 3) * e->width;
-                bool ok = true;
-                if (in == UG_PF_I420) {
-                        ok = !src_pitch || src_pitch == e->width;
-                } else if (in == UG_PF_UYVY || in == UG_PF_RGBA) { // 32-bit words: lines (and the frames of a batch) start at multiples of 4
-                        ok = (!src_pitch || (src_pitch >= line && !(src_pitch & 3))) && !(3 & (uintptr_t) src_dev) && (frames == 1 || !(src_stride & 3));
-                } else if (in == UG_PF_RGB) {
-                        ok = !src_pitch || src_pitch >= line;
-                }
-                if (!ok) {
-                        ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: src_pitch must be 0 or at least the line size (I420: 0 or the width); UYVY and RGBA: "
-                                               "src_dev, src_pitch and src_stride multiples of 4");
-                        return UG_HIP_EINVAL;
-                }
-        }
-        hipStream_t st = (hipStream_t) stream;
+        const Source caller = { in, src_dev, src_pitch, src_stride };
+        int rc = refuse_call(e, caller, frames, out_dev, out_stride, out_capacity, out_len);
+        if (rc != UG_HIP_SUCCESS) return rc;
         if (frames > e->batch_cap) { // the work buffers of a frame, once per frame of the batch (grown once; kernels of earlier calls have finished: encode is synchronous)
                 const hipError_t err = alloc_workspace(e, frames);
                 if (err != hipSuccess) {
@@ -2050,455 +2490,15 @@ int ug_hip_jpeg_encoder_encode_batch(ug_hip_jpeg_encoder *enc, ug_pixfmt_t in, i
                         return UG_HIP_ERUNTIME;
                 }
         }
-        BatchStride bs = strides_of(e);
-        bs.out_bytes = (long) out_stride;
-        int rc = UG_HIP_SUCCESS;
-        const int w = e->width, h = e->height;
-        const int S_frame = e->ri * (e->ybl + e->nc); // blocks per (full) restart segment
-        const bool wave_path = (e->nonint ? e->ri : S_frame) > 256 || e->force_wave_kernel; // (a scan of one component: a segment is ri blocks)
-        if (!src_pitch && in == UG_PF_UYVY) src_pitch = ug::linesize(UG_PF_UYVY, w);
-        // ---- the colour stage (create_ex's internal_cs): the frame(s) converted into a buffer of the encoder's, which then takes the input's place ----
-        const int cs_to = in == UG_PF_RGB ? e->cs_rgb : (in == UG_PF_UYVY ? e->cs_uyvy : 0);
-        if (in == UG_PF_I420 && e->cs_uyvy) {
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: planar input is coded as it comes (no colour conversion)");
-                return UG_HIP_EUNSUPP;
-        }
-        if (cs_to) {
-                if (!src_pitch) src_pitch = 3 * w;
-                const int ls = in == UG_PF_RGB ? 3 * w : ug::linesize(UG_PF_UYVY, w);
-                const size_t fb = ((size_t) ls * h + 15) / 16 * 16;
-                if (e->cs_tmp_bytes < fb * frames) {
-                        if (e->cs_tmp) (void) hipFree(e->cs_tmp);
-                        e->cs_tmp = nullptr;
-                        e->cs_tmp_bytes = 0;
-                        UG_HIP_TRY(hipMalloc((void **) &e->cs_tmp, fb * kMaxBatch));
-                        e->cs_tmp_bytes = fb * kMaxBatch;
-                }
-                const int crc = ug::jpeg_colour_convert(in, in == UG_PF_RGB ? UG_JPEG_CS_RGB : UG_JPEG_CS_YCBCR_BT709, cs_to, src_dev, src_pitch, e->cs_tmp, ls, w, h, frames,
-                                                        src_stride, fb, stream);
-                if (crc != UG_HIP_SUCCESS) return crc;
-                src_dev = e->cs_tmp;
-                src_pitch = ls;
-                src_stride = fb;
-        }
-        if (e->alpha != (in == UG_PF_RGBA)) {
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:4:4:4 encoder takes RGBA, and only it takes RGBA");
-                return UG_HIP_EUNSUPP;
-        }
-        if (e->rgb_sub && in != UG_PF_RGB) {
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:2:x encoder created with UG_JPEG_INPUT_RGB takes RGB only");
-                return UG_HIP_EUNSUPP;
-        }
-        // ---- a 4:4:4 encoder fed UYVY (UG_JPEG_INPUT_UYVY): the frame(s) as 3 B/px in the coded colour space, which then take the place of RGB input ----
-        if (e->sub == 444 && !e->alpha && e->in_uyvy != (in == UG_PF_UYVY)) {
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: a 4:4:4 encoder takes RGB, or UYVY when created with UG_JPEG_INPUT_UYVY");
-                return UG_HIP_EUNSUPP;
-        }
-        if (e->sub == 444 && e->in_uyvy) {
-                const size_t fb = ((size_t) 3 * w * h + 15) / 16 * 16;
-                if (e->cs_tmp_bytes < fb * frames) {
-                        if (e->cs_tmp) (void) hipFree(e->cs_tmp);
-                        e->cs_tmp = nullptr;
-                        e->cs_tmp_bytes = 0;
-                        UG_HIP_TRY(hipMalloc((void **) &e->cs_tmp, fb * kMaxBatch));
-                        e->cs_tmp_bytes = fb * kMaxBatch;
-                }
-                const int crc = ug::jpeg_uyvy_to_444(e->cs_444, src_dev, src_pitch, e->cs_tmp, 3 * w, w, h, frames, src_stride, fb, stream);
-                if (crc != UG_HIP_SUCCESS) return crc;
-                in = UG_PF_RGB;
-                src_dev = e->cs_tmp;
-                src_pitch = 3 * w;
-                src_stride = fb;
-        }
-        // Fused: forward DCT, quantiser, Huffman coding and byte stuffing in ONE kernel, a workgroup per 32 consecutive MCUs -- the quantised
-        // coefficients never reach HBM.  Needs whole segments per workgroup (32 % ri == 0) and the aligned geometry of the fast front end.
-        if (!src_pitch && in == UG_PF_RGB) src_pitch = 3 * w;
-        // a workgroup = 32 (RGB: 64) consecutive MCUs of the scan = whole segments: the restart interval must divide that.  fused_ok: the fused
-        // kernels divide MCU numbers by the MCUs of a row with a multiplication (CodeArgs::mcu_w_m32), exact while (n_mcu + 64) * mcu_w < 2^32
-        // and the row has more than one MCU -- every picture from 9 (17) pixels wide up to ~16K x 16K; others take the two-kernel path
-        const bool fused_ok = e->mcu_w > 1 && ((long) e->n_mcu + 64) * e->mcu_w < (1L << 32);
-        const bool fused_yuv = fused_ok && !wave_path && e->allow_fused && in == UG_PF_UYVY && e->sub != 444 && w % 16 == 0 && !(src_pitch & 15) && !(15 & (uintptr_t) src_dev) &&
-                               (frames == 1 || !(src_stride & 15)) && 32 % e->ri == 0;
-        // packed RGB (4:4:4, R, G, B components): any width and alignment (the edge blocks of the picture are loaded byte by byte)
-        const bool fused_rgb = fused_ok && !wave_path && e->allow_fused && in == UG_PF_RGB && e->sub == 444 && 64 % e->ri == 0 && !e->ycc && !e->nonint;
-        // planar I420: 8-byte row pieces of the three planes (width % 16 == 0 keeps the chroma rows 8-byte aligned too)
-        const bool fused_i420 = fused_ok && !wave_path && e->allow_fused && in == UG_PF_I420 && e->sub == 420 && w % 16 == 0 && (!src_pitch || src_pitch == w) && !(7 & (uintptr_t) src_dev) &&
-                                (frames == 1 || !(src_stride & 7)) && 32 % e->ri == 0;
-        const bool fused = fused_yuv || fused_rgb || fused_i420;
-        if (fused) {
-                // nothing to do here: the coder below reads the frame itself
-        } else if (in == UG_PF_UYVY && e->sub != 444) { // fused unpack + subsample + FDCT + quantise, grid.z = frame
-                rc = ug_hip_uyvy_to_jpeg42x_coeffs_batch(e->sub, src_dev, src_pitch, w, h, e->div, e->cy, e->cb, e->cr, frames, src_stride,
-                                                         (size_t) bs.coef_y * 2, (size_t) bs.coef_c * 2, stream);
-        } else if (in == UG_PF_RGB && e->rgb_sub) { // R, G, B at 4:2:x: R over its full grid, G and B box-averaged, in one pass over the frame(s) (rgb_jpeg42x_kernel)
-                if (!src_pitch) src_pitch = 3 * w;
-                rc = ug::jpeg_fdct_quant_rgb42x(e->sub, src_dev, src_pitch, w, h, e->div, e->cy, e->cb, e->cr, frames, src_stride, (size_t) bs.coef_y * 2,
-                                                (size_t) bs.coef_c * 2, stream);
-        } else if (in == UG_PF_RGB && e->sub == 444) { // GPUJPEG_444_U8_P012, components kept as R, G, B (gpujpeg.cpp:303-305,336)
-                if (!src_pitch) src_pitch = 3 * w;
-                for (int f = 0; f < frames && rc == UG_HIP_SUCCESS; f++) {
-                        const uint8_t *const fr = (const uint8_t *) src_dev + f * src_stride;
-                        if (e->ycc) { // Y', Cb, Cr (the colour stage's output): the luma quantiser for component 0, the chroma one for the others
-                                rc = ug::jpeg_fdct_quant_strided(fr, src_pitch, 3, w, h, e->mcu_w, e->mcu_h, e->div, e->cy + f * bs.coef_y, nullptr, stream);
-                                if (rc == UG_HIP_SUCCESS) rc = ug::jpeg_fdct_quant_strided(fr + 1, src_pitch, 3, w, h, e->mcu_w, e->mcu_h, e->div + 64, e->cb + f * bs.coef_c, nullptr, stream);
-                                if (rc == UG_HIP_SUCCESS) rc = ug::jpeg_fdct_quant_strided(fr + 2, src_pitch, 3, w, h, e->mcu_w, e->mcu_h, e->div + 64, e->cr + f * bs.coef_c, nullptr, stream);
-                        } else {
-                                rc = ug::jpeg_fdct_quant_rgb444(fr, src_pitch, w, h, e->mcu_w, e->mcu_h, e->div, e->cy + f * bs.coef_y, e->cb + f * bs.coef_c, e->cr + f * bs.coef_c, stream);
-                        }
-                }
-        } else if (in == UG_PF_RGBA && e->alpha) { // GPUJPEG_4444_U8_P0123: R, G, B, A in one pass over the frame (rgba_jpeg4444_kernel)
-                if (!src_pitch) src_pitch = 4 * w;
-                for (int f = 0; f < frames && rc == UG_HIP_SUCCESS; f++) {
-                        const uint8_t *const fr = (const uint8_t *) src_dev + f * src_stride;
-                        rc = ug::jpeg_fdct_quant_rgba4444(fr, src_pitch, w, h, e->mcu_w, e->mcu_h, e->div, e->cy + f * bs.coef_y, e->cb + f * bs.coef_c, e->cr + f * bs.coef_c,
-                                                          e->ca + f * bs.coef_c, stream);
-                }
-        } else if (in == UG_PF_I420 && e->sub == 420) { // planar passthrough (GPUJPEG_420_U8_P0P1P2, gpujpeg.cpp:335): Y, U, V planes back to back
-                if (src_pitch && src_pitch != w) {
-                        ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: I420 input must be tightly packed");
-                        return UG_HIP_EINVAL;
-                }
-                const int cw = (w + 1) / 2, ch = (h + 1) / 2;
-                for (int f = 0; f < frames && rc == UG_HIP_SUCCESS; f++) {
-                        const uint8_t *y = (const uint8_t *) src_dev + f * src_stride, *u = y + (size_t) w * h, *v = u + (size_t) cw * ch;
-                        rc = ug::jpeg_fdct_quant_strided(y, w, 1, w, h, 2 * e->mcu_w, 2 * e->mcu_h, e->div, e->cy + f * bs.coef_y, nullptr, stream);
-                        if (rc == UG_HIP_SUCCESS) rc = ug::jpeg_fdct_quant_strided(u, cw, 1, cw, ch, e->mcu_w, e->mcu_h, e->div + 64, e->cb + f * bs.coef_c, nullptr, stream);
-                        if (rc == UG_HIP_SUCCESS) rc = ug::jpeg_fdct_quant_strided(v, cw, 1, cw, ch, e->mcu_w, e->mcu_h, e->div + 64, e->cr + f * bs.coef_c, nullptr, stream);
-                }
-        } else {
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: input must be UYVY (4:2:0 / 4:2:2 encoder), I420 (4:2:0), RGB (4:4:4) or RGBA (4:4:4:4); "
-                                       "convert other formats with ug_hip_pixfmt_convert");
-                return UG_HIP_EUNSUPP;
-        }
+        Call k = { {}, frames, (uint8_t *) out_dev, out_stride, out_capacity, (hipStream_t) stream, strides_of(e), {} };
+        k.bs.out_bytes = (long) out_stride;
+        rc = stage_source(e, caller, frames, stream, &k.src);
         if (rc != UG_HIP_SUCCESS) return rc;
-        e->total_host[kMaxBatch] = 0;
-        // the block-parallel coder, fused or behind the front end; two_launch: slots + gather launch, else the one-launch placement (look-back)
-        // `scan` = nullptr: the frame's one interleaved scan.  Else one scan of a non-interleaved stream: a single component's blocks (its MCU is one block),
-        // its own header bytes, destination and length words; always the one-launch placement
-        struct ScanPlan {
-                const int16_t *coef; int tab0; const uint8_t *header; int header_len; const uint32_t *base; uint32_t *total;
-                int bw, n, gw, n_seg; // the scan's blocks: bw x (n / bw) of a grid gw blocks wide, in n_seg segments (Encoder::scan_*)
-                long stride;          // int16 elements between the frames' planes of the component
-        };
-        auto launch_coder = [&](bool two_launch, const ScanPlan *scan = nullptr) -> int {
-                const int S = scan ? e->ri : S_frame;
-                const bool fused = !scan && (fused_yuv || fused_rgb || fused_i420); // (shadows the call's: a scan of one component reads coefficients)
-                if (++e->gen >= (1u << 30)) { // the status words carry the call's generation in 30 bits: start over on clean words
-                        UG_HIP_TRY(hipMemsetAsync(e->status, 0, (size_t) e->n_mcu * 8 * e->batch_cap, st));
-                        e->gen = 1;
-                }
-                CodeArgs a = {};
-                a.mcu_w = e->mcu_w; a.n_mcu = e->n_mcu; a.hs = e->hs; a.vs = e->vs; a.ctab = e->ctab; a.ri = e->ri; a.n_seg = e->n_seg; a.S = S;
-                a.gw0 = e->hs * e->mcu_w;
-                if (scan) { // a scan of one component: its MCU is one block
-                        a.mcu_w = scan->bw; a.n_mcu = scan->n; a.hs = a.vs = 1; a.n_seg = scan->n_seg; a.gw0 = scan->gw;
-                }
-                a.nc = scan ? 0 : e->nc; a.tab0 = scan ? scan->tab0 : 0;
-                a.cy = scan ? scan->coef : e->cy; a.cb = e->cb; a.cr = e->cr; a.ca = e->ca; a.coef_y = scan ? scan->stride : bs.coef_y; a.coef_c = bs.coef_c;
-                a.src = (const uint8_t *) src_dev; a.pitch = src_pitch; a.width = w; a.height = h; a.src_stride = src_stride;
-                a.out = (uint8_t *) out_dev; a.out_stride = out_stride; a.capacity = out_capacity; a.header = e->header_dev; a.header_len = (int) e->header.size();
-                a.total_pinned = e->total_host_dev;
-                if (scan) {
-                        a.header = scan->header; a.header_len = scan->header_len; a.base = scan->base;
-                        a.total_pinned = scan->total;
-                }
-                a.status = e->status; a.n_status = e->n_mcu; a.gen = e->gen; a.ticket = e->use_ticket ? e->ticket : nullptr; a.prof = e->prof;
-                a.flat = 0; // decided below, once the number of workgroups of a frame is known
-                // divisions by S, blocks per MCU and MCUs per row as multiplications, where the ranges allow (CodeArgs)
-                {
-                        const int per_mcu = a.hs * a.vs + a.nc;
-                        auto m16 = [](int d) { return (uint32_t) (65536 / d + 1); };
-                        auto m32 = [](long d) { return d > 1 ? (uint32_t) ((1ull << 32) / (unsigned long long) d + 1ull) : 0u; };
-                        a.S_m16 = m16(S);             // x < 256 lanes, S <= 256: x * S < 2^16
-                        a.per_mcu_m16 = m16(per_mcu); // x < S <= 256, per_mcu <= 6
-                        a.S_m32 = m32(S);             // x <= S * 16 window words + S
-                        a.mcu_w_m32 = m32(e->mcu_w);  // x < n_mcu + 64 (the lanes of a last, short workgroup): see fused_ok
-                }
-                int waves, kwin = 16;
-                if (fused) {
-                        const int mcus = fused_rgb ? 64 : 32; // MCUs per workgroup
-                        a.n_wg = (e->n_mcu + mcus - 1) / mcus;
-                        a.G = mcus / e->ri;
-                        waves = e->sub == 422 ? 2 : 3;
-                        if (e->sub != 422) kwin = 12;
-                } else {
-                        // waves per workgroup: the count that leaves the fewest lanes idle (fewer waves on a tie)
-                        waves = 1;
-                        for (int k = 1; k <= 4; k++) {
-                                if (64 * k >= S && (64 * k / S) * S * (64 * waves) > (64 * waves / S) * S * (64 * k)) waves = k;
-                                if (64 * waves < S) waves = k;
-                        }
-                        // (the kernel's per-segment LDS words are sized for segments of at least 3 blocks, kMaxSeg = lanes / 3 + 1: the shortest ones an
-                        // interleaved scan has; a one-component scan with restart interval 1 or 2 has shorter ones and leaves lanes idle instead)
-                        a.G = std::min(64 * waves / S, 64 * waves / 3);
-                        a.n_wg = (a.n_seg + a.G - 1) / a.G;
-                }
-                if (a.n_wg > e->n_mcu) { // (the look-back's status words and the workgroups' byte counts: n_mcu per frame; a workgroup codes at least 21 blocks)
-                        ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: more coder workgroups than status words");
-                        return UG_HIP_ERUNTIME;
-                }
-                if (two_launch) {
-                        // a slot holds whatever the one-pass path can produce: every window full, every byte stuffed, the markers (+ the padding the
-                        // gather's word reads may touch); a workgroup on the general path that needs more reports it and the call runs again, one launch
-                        a.slot_bytes = ((size_t) 64 * waves * kwin * 4 * 2 + 2 * (size_t) a.G + 16 + 255) / 256 * 256;
-                        const size_t need = a.slot_bytes * (size_t) a.n_wg * (size_t) frames;
-                        if (need > e->slots_cap) {
-                                if (e->slots) (void) hipFree(e->slots);
-                                e->slots = nullptr;
-                                e->slots_cap = 0;
-                                const size_t want = a.slot_bytes * (size_t) a.n_wg * (size_t) e->batch_cap;
-                                // + 8: the gather reads the stream in 8-byte words and may touch up to 7 bytes past byte n of a slot; a general-path workgroup
-                                // may fill its slot to the last byte, and the last slot of the last frame ends where the allocation would
-                                const hipError_t err = hipMalloc((void **) &e->slots, want + 8);
-                                if (err != hipSuccess) {
-                                        (void) hipGetLastError();
-                                        two_launch = false; // no room for the slots: the one-launch placement needs none
-                                } else {
-                                        e->slots_cap = want;
-                                }
-                        }
-                }
-                if (two_launch) {
-                        a.slots = e->slots;
-                        a.wg_bytes = e->wg_bytes;
-                }
-                // The flat look-back reads n_wg^2 / 2 eight-byte words per frame: 4 MB at 4K (n_wg ~ 1000) -- all L2 hits, 10 % off the one-frame call --,
-                // 64 MB at 8K (-6 %), and it grows with the square: past kFlatMaxWg workgroups a frame the windowed walk (16 round trips per 1024
-                // workgroups) is the cheaper form again (nothing bounded it for the sizes create() accepts, up to 65535 x 65535)
-                constexpr int kFlatMaxWg = 4096;
-                a.flat = frames == 1 && e->flat_lookback && a.n_wg <= kFlatMaxWg ? 1 : 0;
-                const dim3 grid((unsigned) a.n_wg, (unsigned) frames);
-                if (fused) {
-                        if (fused_i420) hipLaunchKernelGGL((jpeg_code_kernel<3, 1420>), grid, dim3(192), 0, st, a, (const float *) e->div);
-                        else if (e->sub == 420) hipLaunchKernelGGL((jpeg_code_kernel<3, 420>), grid, dim3(192), 0, st, a, (const float *) e->div);
-                        else if (e->sub == 422 && frames >= 2) hipLaunchKernelGGL((jpeg_code_kernel<2, 422, true>), grid, dim3(128), 0, st, a, (const float *) e->div);
-                        else if (e->sub == 422) hipLaunchKernelGGL((jpeg_code_kernel<2, 422>), grid, dim3(128), 0, st, a, (const float *) e->div);
-                        else hipLaunchKernelGGL((jpeg_code_kernel<3, 444>), grid, dim3(192), 0, st, a, (const float *) e->div);
-                } else {
-                        switch (waves) {
-                        case 1: hipLaunchKernelGGL((jpeg_code_kernel<1, 0>), grid, dim3(64), 0, st, a, (const float *) e->div); break;
-                        case 2: hipLaunchKernelGGL((jpeg_code_kernel<2, 0>), grid, dim3(128), 0, st, a, (const float *) e->div); break;
-                        case 3: hipLaunchKernelGGL((jpeg_code_kernel<3, 0>), grid, dim3(192), 0, st, a, (const float *) e->div); break;
-                        default: hipLaunchKernelGGL((jpeg_code_kernel<4, 0>), grid, dim3(256), 0, st, a, (const float *) e->div); break;
-                        }
-                }
-                if (two_launch) {
-                        hipLaunchKernelGGL(jpeg_gather_kernel, dim3((unsigned) ((a.n_wg + 3) / 4), (unsigned) frames), dim3(256), 0, st, (const uint8_t *) e->slots, a.slot_bytes,
-                                           (const uint32_t *) e->wg_bytes, a.n_wg, (uint8_t *) out_dev, out_stride, out_capacity, (const uint8_t *) e->header_dev,
-                                           (int) e->header.size(), e->total_host_dev);
-                }
-                return UG_HIP_SUCCESS;
-        };
-        // A scan that is ONE segment (restart_interval 0), coded in parallel (nori_*_kernel above); frame after frame on the stream, one more host synchronisation per frame
-        // (the scan's length in bits, to size the byte-stuffing launches).  scan = nullptr: the interleaved scan.
-        static const bool nori_off = getenv("UG_JPEG_NORI") != nullptr && getenv("UG_JPEG_NORI")[0] == '0';
-        const bool nori = wave_path && !e->force_wave_kernel && e->n_seg == 1 && !nori_off && (unsigned long long) e->cap * 8ull < (1ull << 32); // (UG_JPEG_WAVE_KERNEL=1: the old kernels throughout)
-        auto code_without_restart = [&](const ScanPlan *scan) -> int {
-                const uint32_t n_blocks = scan ? (uint32_t) scan->n : (uint32_t) e->n_mcu * (uint32_t) (e->ybl + e->nc);
-                // (a bit count per block of the largest scan + the total: the R scan of a 4:2:x R, G, B stream has at most ybl * n_mcu blocks)
-                if (!e->nori_bits) UG_HIP_TRY(hipMalloc((void **) &e->nori_bits, ((size_t) e->n_mcu * (e->ybl + e->nc) + 1) * 4));
-                for (int f = 0; f < frames; f++) {
-                        NoriScan s = {};
-                        s.c0 = scan ? scan->coef + f * scan->stride : e->cy + f * bs.coef_y; s.c1 = e->cb + f * bs.coef_c; s.c2 = e->cr + f * bs.coef_c;
-                        s.c3 = e->ca ? e->ca + f * bs.coef_c : nullptr;
-                        s.mcu_w = scan ? scan->bw : e->mcu_w; s.n_mcu = scan ? scan->n : e->n_mcu; s.hs = scan ? 1 : e->hs; s.vs = scan ? 1 : e->vs; s.nc = scan ? 0 : e->nc;
-                        s.tab0 = scan ? scan->tab0 : 0; s.ctab = e->ctab; s.ri = s.n_mcu; s.gw0 = scan ? scan->gw : e->hs * e->mcu_w;
-                        hipLaunchKernelGGL(nori_len_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, e->nori_bits);
-                        hipLaunchKernelGGL(nori_scan_kernel, dim3(1), dim3(1024), 0, st, e->nori_bits, n_blocks);
-                        uint32_t *const bits_host = e->total_host + kOddBlock * kTotalWords; // (a word of the pinned block of its own)
-                        UG_HIP_TRY(hipMemcpyAsync(bits_host, e->nori_bits + n_blocks, 4, hipMemcpyDeviceToHost, st));
-                        UG_HIP_TRY(hipStreamSynchronize(st));
-                        const size_t bytes = ((size_t) *bits_host + 7) / 8;
-                        const uint32_t n_pieces = (uint32_t) ((bytes + 63) / 64);
-                        if (e->nori_ff_cap < (size_t) n_pieces + 1) {
-                                if (e->nori_ff) (void) hipFree(e->nori_ff);
-                                e->nori_ff = nullptr;
-                                e->nori_ff_cap = 0;
-                                UG_HIP_TRY(hipMalloc((void **) &e->nori_ff, ((size_t) n_pieces + 1) * 4 * 2));
-                                e->nori_ff_cap = ((size_t) n_pieces + 1) * 2;
-                        }
-                        UG_HIP_TRY(hipMemsetAsync(e->scratch, 0, (bytes + 8 + 3) & ~(size_t) 3, st));
-                        hipLaunchKernelGGL(nori_emit_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, (const uint32_t *) e->nori_bits, e->scratch, n_blocks, 0u);
-                        if (n_pieces) hipLaunchKernelGGL(nori_ff_kernel, dim3((n_pieces + 255) / 256), dim3(256), 0, st, (const uint32_t *) e->scratch, (const uint32_t *) e->nori_bits + n_blocks, n_pieces, e->nori_ff);
-                        hipLaunchKernelGGL(nori_scan_kernel, dim3(1), dim3(1024), 0, st, e->nori_ff, n_pieces);
-                        hipLaunchKernelGGL(nori_place_kernel, dim3(n_pieces ? (n_pieces + 255) / 256 : 1), dim3(256), 0, st, (const uint32_t *) e->scratch, (const uint32_t *) e->nori_bits + n_blocks,
-                                           n_pieces, (const uint32_t *) e->nori_ff, (uint8_t *) out_dev + (size_t) f * out_stride, scan ? scan->header : (const uint8_t *) e->header_dev,
-                                           scan ? scan->header_len : (int) e->header.size(), out_capacity, scan ? scan->total : e->total_host_dev, scan ? scan->base : nullptr, f);
-                }
-                return UG_HIP_SUCCESS;
-        };
-        // Restart intervals too long for the block coder (more than 256 blocks per segment), SEVERAL segments: the same lane-per-block coding, into the per-segment buffers
-        // of the wave-per-segment coder (bit positions inside a segment by a segmented prefix sum), in front of that coder's compaction kernel -- which moves a segment
-        // per wave, where entropy_wave_kernel CODED a segment per wave, block after block (restart=2000 at 4K: 4 ms).  UG_JPEG_NORI=0: the old kernel.
-        // (which is faster, profiles/r06_encode_no_restart.txt: the old kernel takes ~0.9 us per block of a segment, the segments side by side; this way costs what the picture
-        // costs -- clearing the buffers, two passes over the blocks: ~0.58 ms at 4K -- whatever the interval.  4K: from ~650 blocks per segment, 1080p: from ~290)
-        const bool seg_parallel = wave_path && !e->force_wave_kernel && e->n_seg > 1 && !nori_off &&
-                                  0.9 * (double) e->ri * (e->nonint ? 1 : e->ybl + e->nc) > 150.0 + 5.2e-5 * (double) w * (double) h;
-        auto fill_segments = [&](const ScanPlan *scan) -> int {
-                const uint32_t per_mcu = (uint32_t) (scan ? 1 : e->ybl + e->nc), n_blocks = scan ? (uint32_t) scan->n : (uint32_t) e->n_mcu * per_mcu;
-                const int n_seg = scan ? scan->n_seg : e->n_seg;
-                if (!e->nori_bits) UG_HIP_TRY(hipMalloc((void **) &e->nori_bits, ((size_t) e->n_mcu * (e->ybl + e->nc) + 1) * 4));
-                if (e->nori_ff_cap < (size_t) e->n_seg + 1) {
-                        if (e->nori_ff) (void) hipFree(e->nori_ff);
-                        e->nori_ff = nullptr;
-                        e->nori_ff_cap = 0;
-                        UG_HIP_TRY(hipMalloc((void **) &e->nori_ff, ((size_t) e->n_seg + 1) * 4));
-                        e->nori_ff_cap = (size_t) e->n_seg + 1;
-                }
-                for (int f = 0; f < frames; f++) {
-                        NoriScan s = {};
-                        s.c0 = scan ? scan->coef + f * scan->stride : e->cy + f * bs.coef_y; s.c1 = e->cb + f * bs.coef_c; s.c2 = e->cr + f * bs.coef_c;
-                        s.c3 = e->ca ? e->ca + f * bs.coef_c : nullptr;
-                        s.mcu_w = scan ? scan->bw : e->mcu_w; s.n_mcu = scan ? scan->n : e->n_mcu; s.hs = scan ? 1 : e->hs; s.vs = scan ? 1 : e->vs; s.nc = scan ? 0 : e->nc;
-                        s.tab0 = scan ? scan->tab0 : 0; s.ctab = e->ctab; s.ri = e->ri; s.gw0 = scan ? scan->gw : e->hs * e->mcu_w;
-                        uint32_t *const raw = e->scratch + (size_t) f * bs.raw_words;
-                        hipLaunchKernelGGL(nori_len_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, e->nori_bits);
-                        hipLaunchKernelGGL(nori_segscan_kernel, dim3(1), dim3(1024), 0, st, e->nori_bits, n_blocks, (uint32_t) e->ri * per_mcu, e->nori_ff);
-                        UG_HIP_TRY(hipMemsetAsync(raw, 0, (size_t) n_seg * (size_t) e->cap, st));
-                        hipLaunchKernelGGL(nori_emit_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, s, n_blocks, (const uint32_t *) e->nori_bits, raw, (uint32_t) e->ri * per_mcu,
-                                           (uint32_t) (e->cap / 4));
-                        hipLaunchKernelGGL(nori_segstat_kernel, dim3((n_seg + 3) / 4), dim3(256), 0, st, (const uint32_t *) raw, (uint32_t) (e->cap / 4), (const uint32_t *) e->nori_ff, n_seg,
-                                           e->seg_len + (size_t) f * bs.seg, e->seg_ff + (size_t) f * bs.seg, e->chunk_tot + (size_t) f * bs.tot_words);
-                }
-                return UG_HIP_SUCCESS;
-        };
-        if (e->nonint) {
-                // One scan per component (T.81 A.2.2; the reference's default for RGB input, gpujpeg.cpp:303).  Each scan is the block coder over ONE
-                // component's coefficients -- DC prediction and restart intervals (in blocks) of its own, its markers numbered from RST0 -- preceded by
-                // its header bytes (scan 0: SOI .. SOS; scans 1, 2: their SOS).  Where a scan ends is only known once it is coded: the launch of scan c
-                // reads the length scan c - 1 left behind (CodeArgs::base) and goes on from there, over the EOI every coded stream ends with.  Three
-                // launches on the stream, one synchronisation, no intermediate buffer.
-                const int n_scans = 1 + e->nc;
-                memset(e->total_host, 0, (size_t) (1 + n_scans) * kTotalWords * 4);
-                if (wave_path && frames > e->raw_cap) {
-                        const hipError_t err = alloc_raw(e, e->batch_cap);
-                        if (err != hipSuccess) {
-                                ug::set_last_error(err, "ug_hip_jpeg_encoder_encode: work buffers of the wave-per-segment coder");
-                                free_raw(e);
-                                return UG_HIP_ERUNTIME;
-                        }
-                }
-                for (int c = 0; c < n_scans; c++) {
-                        const int16_t *const planes[4] = { e->cy, e->cb, e->cr, e->ca };
-                        const ScanPlan pl = { planes[c], e->ycc && c > 0 ? 1 : 0, e->scan_header_dev[c], (int) e->scan_header[c].size(),
-                                              c > 0 ? e->total_host_dev + c * kTotalWords : nullptr, e->total_host_dev + (c + 1) * kTotalWords,
-                                              e->scan_bw[c], e->scan_n[c], e->scan_gw[c], e->scan_nseg[c], c > 0 ? bs.coef_c : bs.coef_y };
-                        if (nori) {
-                                const int nrc = code_without_restart(&pl);
-                                if (nrc != UG_HIP_SUCCESS) return nrc;
-                                continue;
-                        }
-                        if (wave_path) { // restart intervals of more than 256 blocks: a wave per segment, then the compaction -- scan after scan on the stream
-                                UG_HIP_TRY(hipMemsetAsync(e->chunk_tot, 0, (size_t) bs.tot_words * 4 * frames, st));
-                                BatchStride bsc = bs; // (the frames' planes of this scan's component)
-                                bsc.coef_y = pl.stride;
-                                if (seg_parallel) {
-                                        const int frc = fill_segments(&pl);
-                                        if (frc != UG_HIP_SUCCESS) return frc;
-                                } else {
-                                        hipLaunchKernelGGL(entropy_wave_kernel, dim3((pl.n_seg + 3) / 4, frames), dim3(256), 0, st, pl.coef, pl.coef, pl.coef, pl.coef, pl.bw, pl.n, 1, 1,
-                                                           pl.gw, 0, 0, pl.tab0, e->ri, pl.n_seg, e->scratch, e->cap / 4, e->seg_len, e->seg_ff, e->chunk_tot, bsc);
-                                }
-                                hipLaunchKernelGGL(compact_kernel, dim3((pl.n_seg + 3) / 4, frames), dim3(256), 0, st, (const uint8_t *) e->scratch, e->cap, e->seg_len, e->seg_ff,
-                                                   e->chunk_tot, pl.n_seg, (uint8_t *) out_dev, pl.header, pl.header_len, out_capacity, pl.total, pl.base, bsc);
-                                continue;
-                        }
-                        const int lrc = launch_coder(false, &pl);
-                        if (lrc != UG_HIP_SUCCESS) return lrc;
-                }
-                UG_HIP_LAUNCH_CHECK();
-                UG_HIP_TRY(hipStreamSynchronize(st));
-                const uint32_t *const t_last = e->total_host + n_scans * kTotalWords; // the last scan's length words
-                uint32_t gave_up = 0;
-                for (int c = 1; c <= n_scans; c++) gave_up |= e->total_host[c * kTotalWords + kMaxBatch];
-                if (gave_up) { // a workgroup gave up waiting for an earlier one (see below): start-order tickets, once more
-                        (void) hipMemset(e->ticket, 0, 4);
-                        if (!e->use_ticket) {
-                                e->use_ticket = true;
-                                fprintf(stderr, "[ug_mi355x] JPEG encoder %dx%d: workgroups did not start in index order; this call is encoded again and the encoder uses "
-                                                "start-order tickets from now on (UG_JPEG_TICKET=1 selects that from the start)\n", e->width, e->height);
-                                return ug_hip_jpeg_encoder_encode_batch(enc, in, frames, src_dev, src_pitch, src_stride, out_dev, out_stride, out_capacity, out_len, stream);
-                        }
-                        ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: the stream placement gave up waiting for an earlier workgroup");
-                        return UG_HIP_ERUNTIME;
-                }
-                bool fits = true;
-                for (int f = 0; f < frames; f++) {
-                        out_len[f] = t_last[f]; // the last scan's end = the stream's length (what it needs, when it does not fit: nothing past the capacity was written)
-                        fits = fits && out_len[f] <= out_capacity;
-                }
-                if (!fits && frames == 1) {
-                        ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: stream does not fit the output buffer (out_len = needed size)");
-                        return UG_HIP_EINVAL;
-                }
-                return UG_HIP_SUCCESS;
-        }
-        e->total_host[kMaxBatch + 1] = 0;
-        if (!wave_path) {
-                // one frame per call: the look-back's waits are short (every workgroup of the frame is resident at once) and the second launch
-                // costs more than it saves (measured 39.4 against 41.3 us per 4K frame); from two frames up the two-launch placement wins
-                const int lrc = launch_coder(e->two_launch && (frames > 1 || e->force_two_launch));
-                if (lrc != UG_HIP_SUCCESS) return lrc;
-        } else {
-                if (frames > e->raw_cap) {
-                        const hipError_t err = alloc_raw(e, e->batch_cap);
-                        if (err != hipSuccess) {
-                                ug::set_last_error(err, "ug_hip_jpeg_encoder_encode: work buffers of the wave-per-segment coder");
-                                free_raw(e);
-                                return UG_HIP_ERUNTIME;
-                        }
-                }
-                if (nori) {
-                        const int nrc = code_without_restart(nullptr);
-                        if (nrc != UG_HIP_SUCCESS) return nrc;
-                } else {
-                // the totals this call's coder adds into start from zero (a smaller batch in between must not leave stale slices behind)
-                UG_HIP_TRY(hipMemsetAsync(e->chunk_tot, 0, (size_t) bs.tot_words * 4 * frames, st));
-                if (seg_parallel) {
-                        const int frc = fill_segments(nullptr);
-                        if (frc != UG_HIP_SUCCESS) return frc;
-                } else {
-                hipLaunchKernelGGL(entropy_wave_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, e->cy, e->cb, e->cr, e->ca ? e->ca : e->cr, e->mcu_w, e->n_mcu,
-                                   e->hs, e->vs, e->hs * e->mcu_w, e->ctab, e->nc, 0, e->ri, e->n_seg, e->scratch, e->cap / 4, e->seg_len, e->seg_ff, e->chunk_tot, bs);
-                }
-                hipLaunchKernelGGL(compact_kernel, dim3((e->n_seg + 3) / 4, frames), dim3(256), 0, st, (const uint8_t *) e->scratch, e->cap, e->seg_len, e->seg_ff, e->chunk_tot,
-                                   e->n_seg, (uint8_t *) out_dev, e->header_dev, (int) e->header.size(), out_capacity, e->total_host_dev, nullptr, bs);
-                }
-        }
-        UG_HIP_LAUNCH_CHECK();
-        UG_HIP_TRY(hipStreamSynchronize(st)); // ONE synchronisation for the batch
-        if (!wave_path && e->total_host[kMaxBatch + 1] != 0) { // a workgroup's bytes did not fit its slot (near-lossless quality on noise): once more, in one launch
-                e->total_host[kMaxBatch + 1] = 0;
-                const int lrc = launch_coder(false);
-                if (lrc != UG_HIP_SUCCESS) return lrc;
-                UG_HIP_LAUNCH_CHECK();
-                UG_HIP_TRY(hipStreamSynchronize(st));
-        }
-        if (e->total_host[kMaxBatch] != 0) { // a workgroup gave up waiting for an earlier one: reported, never waited out
-                (void) hipMemset(e->ticket, 0, 4);
-                if (!e->use_ticket) { // the start order was not the index order after all: from now on the index IS the start order; once more
-                        e->use_ticket = true;
-                        // said once, loudly: the call that met it cost a spin-out (the waiting waves gave up after kSpinLimit polls) and is encoded again, and
-                        // every later call of this encoder takes the ticket form (measured ~8 % of the coder kernel); UG_JPEG_TICKET=1 starts that way
-                        fprintf(stderr, "[ug_mi355x] JPEG encoder %dx%d: a workgroup of the one-launch stream placement waited for a predecessor that had not been "
-                                        "dispatched (workgroups did not start in index order); this call is encoded again and the encoder uses start-order tickets "
-                                        "from now on (UG_JPEG_TICKET=1 selects that from the start)\n", e->width, e->height);
-                        return ug_hip_jpeg_encoder_encode_batch(enc, in, frames, src_dev, src_pitch, src_stride, out_dev, out_stride, out_capacity, out_len, stream);
-                }
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: the stream placement gave up waiting for an earlier workgroup");
-                return UG_HIP_ERUNTIME;
-        }
-        bool fits = true;
-        for (int f = 0; f < frames; f++) {
-                out_len[f] = e->total_host[f];
-                fits = fits && out_len[f] <= out_capacity;
-        }
-        if (!fits && frames == 1) { // segments past the end were not written; out_len tells the caller what it takes
-                ug::set_last_error_msg("ug_hip_jpeg_encoder_encode: stream does not fit the output buffer (out_len = needed size)");
-                return UG_HIP_EINVAL;
-        }
-        // a batch reports per frame: out_len[f] > out_capacity = that stream did not fit (the others are complete)
-        return UG_HIP_SUCCESS;
+        k.pc = choose_path(e, k.src, frames);
+        rc = run_front_end(e, k);
+        if (rc == UG_HIP_SUCCESS) rc = code_streams(e, k);
+        if (rc == UG_HIP_SUCCESS) rc = collect_streams(e, k, out_len);
+        return rc;
 }
 
 } // extern "C"

@@ -27,14 +27,10 @@ using namespace ug_jpeg;
 // store them, then the upper half: 4.5 KB of LDS per wave instead of 9, whole lines per store instruction as before, and a
 // sixth workgroup of the fused UYVY kernel fits the CU.  `lds` = this wave's private kStoreRows x 144 B region; `n_valid`
 // lanes hold real blocks.
-#ifndef UG_JPEG_STORE_HALVES
-#define UG_JPEG_STORE_HALVES 1
-#endif
-constexpr int kStoreRows = UG_JPEG_STORE_HALVES ? 32 : 64;
+constexpr int kStoreRows = 32;
 __device__ __forceinline__ void wave_store_blocks(const uint32_t (&w)[32], uint8_t *lds, int16_t *__restrict__ out_wave,
                                                   int lane, int n_valid)
 {
-#if UG_JPEG_STORE_HALVES
 #pragma unroll
         for (int half = 0; half < 2; half++) {
                 if ((lane >> 5) == half) {
@@ -56,22 +52,6 @@ __device__ __forceinline__ void wave_store_blocks(const uint32_t (&w)[32], uint8
                 __builtin_amdgcn_wave_barrier(); // the rows are overwritten by the other half
                 __builtin_amdgcn_s_waitcnt(0xc07f);
         }
-#else
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-                *(uint4 *) (lds + lane * kLdsPitch + 16 * j) = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
-        }
-        __builtin_amdgcn_wave_barrier(); // same wave wrote and reads: only ordering inside the wave is needed
-        __builtin_amdgcn_s_waitcnt(0xc07f); // lgkmcnt(0)
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-                const int blk = 8 * j + (lane >> 3), piece = lane & 7;
-                const uint4 v = *(const uint4 *) (lds + blk * kLdsPitch + 16 * piece);
-                if (blk < n_valid) {
-                        ((uint4 *) out_wave)[8 * blk + piece] = v;
-                }
-        }
-#endif
 }
 
 // the same for a wave whose lower 32 lanes hold blocks of one plane and whose upper 32 lanes hold blocks of another (Cb | Cr of a strip)
@@ -444,26 +424,7 @@ __device__ __forceinline__ void uyvy_jpeg_fast_body(const uint8_t *__restrict__ 
                 }
                 // lanes 0-31 -> Cb blocks, lanes 32-63 -> Cr blocks of this strip: two contiguous 4 KiB stretches
                 const long first = (long) my * mcu_w + mcu0;
-#if UG_JPEG_STORE_HALVES
                 wave_store_blocks_two(w, lds, out_cb + 64 * first, out_cr + 64 * first, lane, mcus);
-#else
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                        *(uint4 *) (lds + lane * kLdsPitch + 16 * j) = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
-                }
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_s_waitcnt(0xc07f);
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                        const int blk = 8 * j + (lane >> 3), piece = lane & 7; // blk 0-31 Cb, 32-63 Cr
-                        const uint4 v = *(const uint4 *) (lds + blk * kLdsPitch + 16 * piece);
-                        const int mm = blk & 31;
-                        if (mm < mcus) {
-                                int16_t *o = (blk < 32 ? out_cb : out_cr) + 64 * (first + mm);
-                                ((uint4 *) o)[piece] = v;
-                        }
-                }
-#endif
         }
 }
 
