@@ -502,7 +502,23 @@ struct Loader<UG_PF_V210> {
 // No operand comes anywhere near 2^-124, below which a product by 1/32 would be denormal.  Overflow is out of the question
 // (|values| < 16).  The reference writes one operation per product: (t + b) * 0.25 here, and so on at every site.
 
-// ConvertRGBToYCoCg (glsl:27-34, the first lines of the block comment above): (r, g, b) in p.a / p.b / p.c -> (4 Y, Co, Cg) in place
+//
+// The difference domain (PAIRS).  The reference reaches Co and Cg through d = r - b and e = fma(g, 2, -r) - b:
+//   Co = f(d) = RN(d / 2 + off),   Cg = f'(e) = RN(e / 4 + off).
+// d / 2 and e / 4 are exact, + off is monotone in real arithmetic and RN is monotone non-decreasing, so f and f' are monotone
+// non-decreasing maps of fp32 to fp32, and a monotone map commutes with min and max: min_i f(d_i) = f(min_i d_i), the SAME float,
+// bit for bit, and so for max and for f'.  No NaN occurs (|d|, |e| < 4), and d = -0 gives off as +0 does.  So for chroma-pair
+// loaders the pixels stay (4 Y, d, e): the box is taken over d and e and its FOUR ends go through f / f' -- the reference's own
+// mnCo .. mxCg, from all sixteen pixels -- instead of all thirty-two values.  What else read Co[i] / Cg[i] on the main line, the
+// diagonal's rough sum and the colour stage's projection, only locates under a certificate and takes d, e as they are (1/2, 1/4 and
+// off folded into its constants: derived at each); the reference-form sides (exact covariance, per-pixel distances, full form,
+// flat blocks) form Co[i] = f(d[i]), Cg[i] = f'(e[i]) behind their own branch, the reference's operations in the reference's order.
+// tests/test_dxt_pair_difference_bound.py checks the ends on every block of its frames and the monotonicity over the d and e of
+// every (y, u, v) of bytes.
+
+// ConvertRGBToYCoCg (glsl:27-34, the first lines of the block comment above): (r, g, b) in p.a / p.b / p.c -> (4 Y, Co, Cg) in place;
+// PAIRS: -> (4 Y, d, e), the reference's own intermediate values
+template <bool PAIRS>
 __device__ __forceinline__ void convert_rgb_to_ycocg(Px16 &p)
 {
 #pragma unroll
@@ -510,10 +526,32 @@ __device__ __forceinline__ void convert_rgb_to_ycocg(Px16 &p)
                 const float r = p.a[i], g = p.b[i], b = p.c[i];
                 const float t = __builtin_fmaf(g, 2.0f, r);
                 p.a[i] = t + b; // Y4 = 4 Y
-                p.b[i] = __builtin_fmaf(r - b, 0.5f, kOffset);
-                p.c[i] = __builtin_fmaf(__builtin_fmaf(g, 2.0f, -r) - b, 0.25f, kOffset);
+                if constexpr (PAIRS) {
+                        p.b[i] = r - b;
+                        p.c[i] = __builtin_fmaf(g, 2.0f, -r) - b;
+                } else {
+                        p.b[i] = __builtin_fmaf(r - b, 0.5f, kOffset);
+                        p.c[i] = __builtin_fmaf(__builtin_fmaf(g, 2.0f, -r) - b, 0.25f, kOffset);
+                }
         }
 }
+// Co / Cg of a pixel from what the conversion left in p.b / p.c: f(d), f'(e) for PAIRS, the value itself otherwise.  `off` is kOffset;
+// a reference-form side hands in its own copy (side_offset): to the compiler the sides' values then have nothing in common, and it
+// cannot make the later sides' "redundant" by computing all thirty-two ahead of the first branch (which it does otherwise).  The
+// copy is made by the asm's own instruction, so that it stays on the side, too.
+template <bool PAIRS>
+__device__ __forceinline__ float side_offset()
+{
+        float off = kOffset;
+        if constexpr (PAIRS) {
+                asm volatile("v_mov_b32_e32 %0, %1" : "=v"(off) : "i"(__builtin_bit_cast(uint32_t, kOffset)));
+        }
+        return off;
+}
+template <bool PAIRS>
+__device__ __forceinline__ float co_of(float x, float off) { return PAIRS ? __builtin_fmaf(x, 0.5f, off) : x; }
+template <bool PAIRS>
+__device__ __forceinline__ float cg_of(float x, float off) { return PAIRS ? __builtin_fmaf(x, 0.25f, off) : x; }
 
 // FindMinMaxColorsBox (glsl:69-78).  Y[] holds Y4, and so do mnY / mxY
 __device__ __forceinline__ void find_min_max_colors_box(const float *Y, const float *Co, const float *Cg, float &mnY, float &mxY, float &mnCo,
@@ -529,8 +567,10 @@ __device__ __forceinline__ void find_min_max_colors_box(const float *Y, const fl
 }
 
 // SelectYCoCgDiagonal (glsl:169-183): sequential sum, i = 0..15.  True where the covariance is negative: the caller swaps the Cg ends.
+// PAIRS: Co[] / Cg[] hold d / e (the difference domain, at the conversion), mnd .. mxe are their box; mnCo .. mxCg are the reference's ends.
 template <bool PAIRS>
-__device__ __forceinline__ bool select_ycocg_diagonal(const float *Co, const float *Cg, float mnCo, float mxCo, float mnCg, float mxCg)
+__device__ __forceinline__ bool select_ycocg_diagonal(const float *Co, const float *Cg, float mnCo, float mxCo, float mnCg, float mxCg,
+                                                      float mnd, float mxd, float mne, float mxe)
 {
         if constexpr (!PAIRS) {
                 const float midx = (mxCo + mnCo) * 0.5f, midy = (mxCg + mnCg) * 0.5f;
@@ -559,31 +599,56 @@ __device__ __forceinline__ bool select_ycocg_diagonal(const float *Co, const flo
                 // |2 rough - cov| < 0.04 eps over its content).  The 2 is folded into the constant.  These fma only locate; no
                 // result of theirs is an operation of the reference.
                 // Exactly flat axis, hx hy == 0: with Co flat midx is mxCo itself (2 x * 0.5), every tx is exactly 0, the reference's
-                // cov is +-0 and it does not swap; with Cg flat the swap exchanges equal values.  rough is +-0 in both and rough < 0 is false:
-                // the same rule serves, and such blocks are certified without the comparison.
+                // cov is +-0 and it does not swap; with Cg flat the swap exchanges equal values.  Such blocks are certified without the
+                // comparison (for a sum over Co / Cg themselves rough would be +-0 in both; for the sum actually formed see the end of the next paragraph).
                 // A wave that holds a block the certificate does not cover (smooth content: one chroma sample under varying luma leaves
                 // spreads of rounding size) evaluates the reference's sum for all of its blocks and decides from it.
-                const float midx = (mxCo + mnCo) * 0.5f, midy = (mxCg + mnCg) * 0.5f;
+                //
+                // In the difference domain.  The sum is taken over tx' = d - midd, ty' = e - mide with midd = (mxd + mnd) / 2,
+                // mide = (mxe + mne) / 2: in real arithmetic tx' = 2 tx and ty' = 4 ty, so the sum is 8 rough and is compared with 8 x the
+                // bound.  What is new in |rough' / 4 - cov| (rough' / 4 standing for 2 rough), with u = 2^-24:
+                //   tx - tx' / 2 = rho_i - (rho_mx + rho_mn) / 2 - mu_x + mu_d / 2:  Co's own rounding at the pixel and at the two ends
+                //   (|Co| < 2: <= u each), the rounding of midx (the reference's; counted here, not left to the slack) and of midd
+                //   (|mxd + mnd| < 4: <= 2 u, halved, and halved again into tx's scale), |.| <= 3.5 u = 2.1e-7 =: dx; ty - ty' / 4 the
+                //   same with |Cg| < 2, |mxe + mne| < 8 (4 u, halved, quartered): <= 3.5 u = dy.  Per product dx |ty| + |tx| dy + dx dy with
+                //   |tx| <= hx / 2, |ty| <= hy / 2; sixteen of them (eight, doubled): 1.7e-6 (hx + hy) + 7e-13.
+                //   tx', ty' round as tx, ty do (relative u on each factor): 8 * 2 u * 2 hx hy / 4 = 5e-7 hx hy.
+                // With the terms above: |rough' / 4 - cov| < 3.7e-6 (hx + hy) + 6.5e-6 hx hy + 7e-13.  hx <= 1.96 and hy <= 1.36 (the YUV
+                // front ends' ranges), so hx hy <= 0.8 (hx + hy) and 2 x that stays under
+                //   eps = 1e-5 (hx + hy + hx hy) + 1.5e-12:
+                // the present factor still covers the (hx + hy) and hx hy terms; the absolute term is new (the product of two
+                // differences of rounding size, which spreads of a few ulp do not bound) and rides in the fma that scales the bound.
+                // tests/test_dxt_pair_difference_bound.py restates this form in strict fp32 and holds |rough' / 4 - cov| to eps / 4.
+                // Exactly flat Co: mnCo == mxCo no longer implies mnd == mxd -- two d an ulp apart can round to one Co -- so rough' may
+                // be non-zero, of either sign, on a block whose every tx is 0 in the reference (cov = +-0: no swap).  The swap is
+                // therefore rough' < 0 AND hx != 0 (lane masks, on the scalar unit).  Such blocks exist for UYVY bytes: the test
+                // finds them by enumeration (one chroma sample under two lumas; 1.75 million (u, v, y, y') of those it tries have
+                // rough' < 0).  Their Cg spread is of rounding size as well, and on the 400 000 looked at the exchanged ends quantise
+                // to the same codes: the rule is what makes mnCg / mxCg the reference's floats, which the contract asks for, not
+                // something a byte of output has shown so far.  With Cg flat the swap exchanges equal values and nothing is needed.
+                const float midd = (mxd + mnd) * 0.5f, mide = (mxe + mne) * 0.5f;
                 const float hx = mxCo - mnCo, hy = mxCg - mnCg;
                 float rough = 0.0f;
 #pragma unroll
                 for (int i = 0; i < 16; i += 2) {
-                        rough = __builtin_fmaf(Co[i] - midx, Cg[i] - midy, rough);
+                        rough = __builtin_fmaf(Co[i] - midd, Cg[i] - mide, rough);
                 }
-                const lanemask_t certain = LANEMASK(fabsf(rough) > 0.5e-5f * __builtin_fmaf(hx, hy, hx + hy)) | LANEMASK(hx * hy == 0.0f);
+                const lanemask_t certain = LANEMASK(fabsf(rough) > __builtin_fmaf(__builtin_fmaf(hx, hy, hx + hy), 4e-5f, 6e-12f)) | LANEMASK(hx * hy == 0.0f);
                 bool swap;
                 if (__builtin_expect(certain == LANEMASK(true), 1)) { // __all, on the two comparisons' own lane masks
-                        swap = rough < 0.0f;
+                        swap = (rough < 0.0f) & (hx != 0.0f);
                 } else {
-                        // The empty asm keeps this a real branch (see the alpha stage's fallback); the mids pass through it so that
-                        // this side forms its own differences: shared with the even pixels' above they would stay in registers up to here.
-                        float mx = midx, my = midy;
-                        asm volatile("; exact covariance" : "+v"(mx), "+v"(my) :: "memory");
+                        // The empty asm keeps this a real branch (see the alpha stage's fallback); the reference's mids are formed behind it,
+                        // from ends that pass through it, and so are Co[i] / Cg[i]: nothing of this side is computed ahead of the branch.
+                        float x0 = mnCo, x1 = mxCo, y0 = mnCg, y1 = mxCg;
+                        asm volatile("; exact covariance" : "+v"(x0), "+v"(x1), "+v"(y0), "+v"(y1) :: "memory");
+                        const float off = side_offset<PAIRS>();
                         count_exact_cov();
+                        const float mx = (x1 + x0) * 0.5f, my = (y1 + y0) * 0.5f;
                         float cov = 0.0f;
 #pragma unroll
                         for (int i = 0; i < 16; i++) {
-                                const float tx = Co[i] - mx, ty = Cg[i] - my;
+                                const float tx = co_of<PAIRS>(Co[i], off) - mx, ty = cg_of<PAIRS>(Cg[i], off) - my;
                                 cov = cov + tx * ty;
                         }
                         swap = cov < 0.0f;
@@ -594,8 +659,9 @@ __device__ __forceinline__ bool select_ycocg_diagonal(const float *Co, const flo
 
 // The reference's form of EmitIndicesYCoCgDXT5 (glsl:217-250), for the waves the fast stage in encode_dxt5ycocg does not take.  The four squared
 // distances of TWO horizontally adjacent pixels are computed with packed fp32 (v_pk_add/v_pk_mul: IEEE per component, so
-// bit-identical to the scalar form).
-__device__ __forceinline__ uint32_t emit_indices_ycocg_full_form(const float *Co, const float *Cg, const float (&cx)[4], const float (&cy)[4])
+// bit-identical to the scalar form).  PAIRS: Co[] / Cg[] hold d / e, and the pixels' Co / Cg are formed here.
+template <bool PAIRS>
+__device__ __forceinline__ uint32_t emit_indices_ycocg_full_form(const float *Co, const float *Cg, const float (&cx)[4], const float (&cy)[4], float off)
 {
         uint32_t w_cidx = 0;
         f32x2 cx2[4], cy2[4];
@@ -606,7 +672,7 @@ __device__ __forceinline__ uint32_t emit_indices_ycocg_full_form(const float *Co
         }
 #pragma unroll
         for (int i = 14; i >= 0; i -= 2) { // pixel pairs, last first: bits are shifted in MSB first
-                const f32x2 co = { Co[i], Co[i + 1] }, cg = { Cg[i], Cg[i + 1] };
+                const f32x2 co = { co_of<PAIRS>(Co[i], off), co_of<PAIRS>(Co[i + 1], off) }, cg = { cg_of<PAIRS>(Cg[i], off), cg_of<PAIRS>(Cg[i + 1], off) };
                 f32x2 d[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
@@ -624,13 +690,16 @@ __device__ __forceinline__ uint32_t emit_indices_ycocg_full_form(const float *Co
 template <bool AWAY, bool PAIRS>
 __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &tab)
 {
-        convert_rgb_to_ycocg(p);
-        const float *Y = p.a, *Co = p.b, *Cg = p.c; // Y[] holds Y4, and so do mnY / mxY up to InsetYBBox
+        convert_rgb_to_ycocg<PAIRS>(p);
+        const float *Y = p.a, *Co = p.b, *Cg = p.c; // Y[] holds Y4, and so do mnY / mxY up to InsetYBBox.  PAIRS: Co[] / Cg[] hold d / e (co_of, cg_of)
 
         float mnY, mxY, mnCo, mxCo, mnCg, mxCg;
         find_min_max_colors_box(Y, Co, Cg, mnY, mxY, mnCo, mxCo, mnCg, mxCg);
+        // PAIRS: that was the box of d and e; its ends through the monotone maps are the reference's ends, bit for bit (the difference domain, at the conversion)
+        const float mnd = mnCo, mxd = mxCo, mne = mnCg, mxe = mxCg;
+        mnCo = co_of<PAIRS>(mnd, kOffset); mxCo = co_of<PAIRS>(mxd, kOffset); mnCg = cg_of<PAIRS>(mne, kOffset); mxCg = cg_of<PAIRS>(mxe, kOffset);
 
-        if (select_ycocg_diagonal<PAIRS>(Co, Cg, mnCo, mxCo, mnCg, mxCg)) {
+        if (select_ycocg_diagonal<PAIRS>(Co, Cg, mnCo, mxCo, mnCg, mxCg, mnd, mxd, mne, mxe)) {
                 const float t = mxCg; mxCg = mnCg; mnCg = t;
         }
 
@@ -954,6 +1023,14 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 //                  1.2) u / l, in kc: 2 u / l;  kc's product and sum: (1 + 1.42) u / l;  the inner fma at magnitude <= (1.2 +
                 //                  1.42) / l: 2.6 u / l;  the outer one and the two of r and dist at magnitude <= 3: negligible beside these.
                 //                  9.7 u / l = 5.8e-7 / l in s, 1.75e-6 / l in thirds.
+                //                  In the difference domain (the form below: s = fma(d, ka / 2, fma(e, kb / 4, kc')), kc' = fma(off - cx0, ka,
+                //                  (off - cy0) kb), against the projection of the reference's own fp32 Co / Cg) the operands are smaller:
+                //                  |d| / 2 <= 0.98, |e| / 4 <= 0.68, |off - c0| <= 0.71 as a vector and <= 0.51 per coordinate.  ka, kb rounded,
+                //                  in the pixel's fma: (0.98 + 0.68) u / l, in kc': (0.51 + 0.51) u / l;  off - cx0, off - cy0 round at
+                //                  magnitude <= 1/2 (u / 4 each, times |k|): 0.5 u / l;  kc's product and sum: (0.51 + 0.71) u / l;  the inner fma
+                //                  at magnitude <= (0.68 + 0.71) / l: 1.39 u / l;  and Co's, Cg's own rounding, which the pixel no longer carries
+                //                  into the projection but the reference's pixel has: |rho . k| <= 1.42 u / l.  7.2 u / l = 4.3e-7 / l in s,
+                //                  1.3e-6 / l in thirds: under the 1.75e-6 / l the constants were set for, which stay as they are.
                 //   the pair       the odd pixel is within 3.5 * 2^-23 in Co and 4 * 2^-23 in Cg of the even one (the pair-location
                 //                  comment): |dp . k| <= 6.4e-7 / l in s, 1.9e-6 / l in thirds.
                 //   c2, c3         each coordinate is two products and a sum below 1 (2^-25, 2^-26, 2^-25) with weights off 1/3, 2/3 by
@@ -992,8 +1069,10 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         if constexpr (kProjection) {
                                 const float rvv = __builtin_amdgcn_rcpf(vv);
                                 const float ka = vx * rvv, kb = vy * rvv;
-                                // (kc locates only, so it rounds twice; the derivation above counts both)
-                                const float kc = __builtin_fmaf(-cx[0], ka, -cy[0] * kb);
+                                // the pixels are (d, e): Co ka + Cg kb + kc = d (ka / 2) + e (kb / 4) + (off - cx0) ka + (off - cy0) kb, the two
+                                // scalings exact (kc' locates only, so it rounds twice; the derivation above counts both)
+                                const float ka2 = ka * 0.5f, kb4 = kb * 0.25f;
+                                const float kc = __builtin_fmaf(kOffset - cx[0], ka, (kOffset - cy[0]) * kb);
                                 uint32_t jw = 0;      // kIndexBits + j per pair, 4 bits apart
                                 float worst = 0.0f;   // the block's largest |3 s - j|
 #pragma unroll
@@ -1002,7 +1081,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
 #pragma unroll
                                         for (int h = 1; h >= 0; h--) {
                                                 const int i = 4 * grp + 2 * h;
-                                                const float s = clamp01(__builtin_fmaf(Co[i], ka, __builtin_fmaf(Cg[i], kb, kc)));
+                                                const float s = clamp01(__builtin_fmaf(Co[i], ka2, __builtin_fmaf(Cg[i], kb4, kc)));
                                                 const float r = __builtin_fmaf(s, 3.0f, kIndexBias); // the integer 2^23 + j
                                                 jw = (jw << 4) + __float_as_uint(r);
                                                 dist[h] = __builtin_fmaf(s, 3.0f, kIndexBias - r);   // 3 s - j: the difference is exact
@@ -1023,6 +1102,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                         // this side forms its own reciprocal and constants: nothing of it is computed ahead of the branch.
                                         float vw = vv;
                                         asm volatile("; per-pixel distances" : "+v"(vw) :: "memory");
+                                        const float off = side_offset<PAIRS>();
                                         count_exact_pair();
                                         write_rows(cx[0], cy[0], cx[1], cy[1], cx[2], cy[2], cx[3], cy[3]);
                                         const float inv = 1.5f * __builtin_amdgcn_rcpf(vw);
@@ -1031,7 +1111,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                         uint32_t zones = 0, open = 0; // 2-bit zone per pixel; the open comparison's result, one bit per pixel
 #pragma unroll
                                         for (int i = 14; i >= 0; i -= 2) {
-                                                const float s = clamp01(__builtin_fmaf(Co[i], za, __builtin_fmaf(Cg[i], zb, zc)));
+                                                const float s = clamp01(__builtin_fmaf(co_of<PAIRS>(Co[i], off), za, __builtin_fmaf(cg_of<PAIRS>(Cg[i], off), zb, zc)));
                                                 zones = (zones << 4) + __float_as_uint(__builtin_fmaf(s, 2.0f, kIndexBias)); // kIndexBits + 0, 1, 2
                                         }
                                         zones -= index_bias_sum(8, 4);
@@ -1039,7 +1119,8 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
 #pragma unroll
                                         for (int i = 15; i >= 0; i--) { // the pixel's zone sits in bits 2 i, 2 i + 1; a row is 64 float4
                                                 const float4 q = *(const float4 *) ((const char *) tc + (((zones >> (2 * i)) & 3u) << 10));
-                                                const float ax = Co[i] - q.x, ay = Cg[i] - q.y, bx = Co[i] - q.z, by = Cg[i] - q.w;
+                                                const float co = co_of<PAIRS>(Co[i], off), cg = cg_of<PAIRS>(Cg[i], off); // the reference's pixel, formed on this side only
+                                                const float ax = co - q.x, ay = cg - q.y, bx = co - q.z, by = cg - q.w;
                                                 const float da = ax * ax + ay * ay, db = bx * bx + by * by; // glsl:231-235, same operation order
                                                 open = shift_in(open, LANEMASK(da > db));
                                         }
@@ -1093,6 +1174,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                         }
                         if (__any(flat)) {
                                 asm volatile("; flat blocks" ::: "memory");
+                                const float off = side_offset<PAIRS>();
                                 float4 p02, p13; // the palette, back from the table (not kept in registers) where the table holds it
                                 if constexpr (kProjection) {
                                         p02 = make_float4(cx[0], cy[0], cx[2], cy[2]); p13 = make_float4(cx[1], cy[1], cx[3], cy[3]);
@@ -1100,10 +1182,11 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                         p02 = tc[0 * 64]; p13 = tc[2 * 64];
                                 }
                                 const float px[4] = { p02.x, p13.x, p02.z, p13.z }, py[4] = { p02.y, p13.y, p02.w, p13.w };
+                                const float co0 = co_of<PAIRS>(Co[0], off), cg0 = cg_of<PAIRS>(Cg[0], off); // pixel 0 stands for all sixteen
                                 float d[4];
 #pragma unroll
                                 for (int k = 0; k < 4; k++) {
-                                        const float tx = Co[0] - px[k], ty = Cg[0] - py[k];
+                                        const float tx = co0 - px[k], ty = cg0 - py[k];
                                         d[k] = tx * tx + ty * ty;
                                 }
                                 w_cidx = flat ? palette_index(d[0], d[1], d[2], d[3]) * 0x55555555u : w_cidx;
@@ -1111,7 +1194,7 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 } else {
                         asm volatile("; colour index full form" ::: "memory");
                         count_full_form(0);
-                        w_cidx = emit_indices_ycocg_full_form(Co, Cg, cx, cy);
+                        w_cidx = emit_indices_ycocg_full_form<PAIRS>(Co, Cg, cx, cy, side_offset<PAIRS>());
                 }
         }
 
