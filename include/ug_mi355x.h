@@ -256,18 +256,24 @@ int ug_hip_dxt_encode_stats(unsigned long long full_form_waves[2], int reset);
  * covariance (glsl:169-183) from one product per chroma pair wherever an error bound decides it; a wave that holds a block the bound
  * does not decide forms the reference's 16-term sum for all of its blocks.  In the same way its colour stage takes the colour index
  * of a chroma pair (glsl:231-244) from the projection of the pair's even pixel on the palette segment wherever an error bound decides it
- * for both pixels; a wave that holds a block the bound does not decide evaluates the reference's two squared distances for every pixel of
- * all of its blocks.  counts[0 .. n - 1], n = 0 .. 4, receive { colour full form, alpha full form, waves that formed the reference's
- * covariance sum, waves that evaluated the per-pixel distances after the projection }.  A reset through either function clears all four. */
+ * for both pixels; a wave that holds a pair the bound does not decide evaluates the reference's two squared distances for the pixels of
+ * the pair slots that hold such a pair.  counts[0 .. n - 1], n = 0 .. 4, receive { colour full form, alpha full form, waves that formed the reference's
+ * covariance sum, waves that evaluated per-pixel distances after the projection }.  A reset through either function clears all four. */
 int ug_hip_dxt_encode_stats_ex(unsigned long long *counts, int n, int reset);
 /* A fifth count, through an entry point of its own (the one above keeps refusing n > 4).  From a 4:2:2 source the DXT5-YCoCg encoder
  * takes the 3-bit alpha count of a pixel (glsl:262-312) from the pixel's location among the thresholds, RN(7 - (a - min) * 7 / range),
  * wherever an error bound keeps every pixel of the block away from a threshold; a wave that holds a block the bound does not decide
  * forms the reference's thresholds and evaluates the reference's comparison for every pixel of all of its blocks.  *exact_waves (may be
  * NULL) receives the number of such waves since the last reset on the current device.  Content with flat chroma and few luma levels
- * puts a pixel on the middle threshold in most blocks: there every wave counts.  A reset through any of the three functions clears all
- * five counts.  Synchronises the device. */
+ * puts a pixel on the middle threshold in most blocks: there every wave counts.  A reset through any of the stats functions clears all
+ * counts.  Synchronises the device. */
 int ug_hip_dxt_encode_stats_alpha(unsigned long long *exact_waves, int reset);
+/* A sixth count, of the work behind counts[3] above.  A block holds eight chroma pairs, pair slots 0 .. 7.  A wave that holds an
+ * uncertified pair keeps the projection's index for every certified pair and evaluates the reference's distances for the two pixels of
+ * each pair slot in which one of its blocks holds an uncertified pair.  *slot_evaluations (may be NULL) receives the number of such
+ * (wave, slot) evaluations since the last reset on the current device: between 1 and 8 for every wave of counts[3].  A reset through
+ * any of the stats functions clears all counts.  Synchronises the device. */
+int ug_hip_dxt_encode_stats_pair_slots(unsigned long long *slot_evaluations, int reset);
 /* Diagnostics (tests, profiling): what the last call of an LDGM session (below) issued -- kernel launches, host <-> device copies (the
  * schedule upload included) and levels of its decode schedule.  Any pointer may be NULL.  Does not touch the device. */
 typedef struct ug_hip_ldgm ug_hip_ldgm;

@@ -161,47 +161,44 @@ constexpr uint32_t index_bias_sum(int fields, int shift)
 // DXT5-YCoCg colour stage, chroma pairs: the certificate of the index taken from the projection (derived at the stage),
 //   eps = (kProjEpsSeg sqrt(vv) + kProjEpsDiag sqrt(dmax) + kProjEpsDmax dmax) / vv,   in thirds of the palette segment
 constexpr float kProjEpsSeg = 8.5e-6f, kProjEpsDiag = 7.2e-6f, kProjEpsDmax = 4.3e-6f;
-// Diagnostics (ug_hip_dxt_encode_stats): waves that left a fast index stage for the reference's full form, counted in those (cold) paths only
-__device__ unsigned long long g_full_form_waves[2]; // [0] colour indices, [1] alpha indices
-__device__ __forceinline__ void count_full_form(int which)
+// Diagnostics: waves that left a certified or fast stage for a reference-form side, counted in those sides only.  None of the sides is
+// rare on all content -- the per-pixel distances take a few percent of the waves of ordinary video, the exact covariance half the
+// waves of flat-chroma content -- and atomics on ONE address are served one after the other: 129 600 counting waves per launch cost
+// 1.4 ms beside 0.14 ms of encoding, 62 000 of them 0.6 ms.  So every count is kept in kPairSlots slots, each in a 128-byte line of its
+// own, chosen by workgroup and wave; the ug_hip_dxt_encode_stats* functions add them up.
+constexpr int kPairSlots = 256, kPairSlotStride = 16; // 16 x 8 B = one line
+constexpr int kCounterWords = kPairSlots * kPairSlotStride;
+// BY_WAVE = false chooses the slot by workgroup alone: for the count that every kernel of this file holds, so that none of them keeps
+// threadIdx.y alive for a cold side (the chroma-pair kernels keep it anyway)
+template <bool BY_WAVE = true>
+__device__ __forceinline__ void count_slotted(unsigned long long *lines, unsigned long long n)
 {
         if ((int) threadIdx.x == __builtin_amdgcn_readfirstlane((int) threadIdx.x)) {
-                atomicAdd(&g_full_form_waves[which], 1ull);
+                // block = 64 lanes x up to 4 waves; the wave's number is uniform, and said to be: the slot and its address stay scalar
+                const uint32_t wave = BY_WAVE ? (uint32_t) __builtin_amdgcn_readfirstlane((int) threadIdx.y) : 0u;
+                const uint32_t slot = ((blockIdx.x + 17u * blockIdx.y + 101u * blockIdx.z) * 4u + wave) & (kPairSlots - 1);
+                atomicAdd(&lines[slot * kPairSlotStride], n);
         }
 }
+// ug_hip_dxt_encode_stats: waves that left a fast index stage for the reference's full form
+__device__ unsigned long long g_full_form_waves[2][kCounterWords]; // [0] colour indices, [1] alpha indices
+__device__ __forceinline__ void count_full_form(int which) { count_slotted<false>(g_full_form_waves[which], 1ull); }
 // the same for the diagonal stage (ug_hip_dxt_encode_stats_ex): waves that formed the reference's covariance sum.  A counter of its own:
 // the two above keep meaning what they meant.
-__device__ unsigned long long g_exact_cov_waves;
-__device__ __forceinline__ void count_exact_cov()
-{
-        if ((int) threadIdx.x == __builtin_amdgcn_readfirstlane((int) threadIdx.x)) {
-                atomicAdd(&g_exact_cov_waves, 1ull);
-        }
-}
-// and for the colour stage's index from the projection: waves that went on to the per-pixel distances.  That side is no rare
-// path -- a few percent of the waves of ordinary video take it, all of them on content built for it -- and atomics on ONE address are served
-// one after the other: 129 600 counting waves per launch cost 1.4 ms beside 0.14 ms of encoding.  So the count is kept in kPairSlots
-// slots, each in a 128-byte line of its own, chosen by workgroup and wave; ug_hip_dxt_encode_stats_ex adds them up.
-constexpr int kPairSlots = 256, kPairSlotStride = 16; // 16 x 8 B = one line
-__device__ unsigned long long g_exact_pair_waves[kPairSlots * kPairSlotStride];
-__device__ __forceinline__ void count_exact_pair()
-{
-        if ((int) threadIdx.x == __builtin_amdgcn_readfirstlane((int) threadIdx.x)) {
-                const uint32_t slot = ((blockIdx.x + 17u * blockIdx.y + 101u * blockIdx.z) * 4u + threadIdx.y) & (kPairSlots - 1); // block = 64 lanes x up to 4 waves
-                atomicAdd(&g_exact_pair_waves[slot * kPairSlotStride], 1ull);
-        }
-}
+__device__ unsigned long long g_exact_cov_waves[kCounterWords];
+__device__ __forceinline__ void count_exact_cov() { count_slotted(g_exact_cov_waves, 1ull); }
+// and for the colour stage's index from the projection: waves that went on to the per-pixel distances
+__device__ unsigned long long g_exact_pair_waves[kCounterWords];
+__device__ __forceinline__ void count_exact_pair() { count_slotted(g_exact_pair_waves, 1ull); }
+// of those waves, the pair slots (0 .. 7) in which a lane held an uncertified pair and whose two pixels got the distances: one
+// addition per wave of what its slot branches counted (ug_hip_dxt_encode_stats_pair_slots)
+__device__ unsigned long long g_pair_slot_evaluations[kCounterWords];
+__device__ __forceinline__ void count_pair_slots(uint32_t n) { count_slotted(g_pair_slot_evaluations, n); }
 // and for the alpha stage's count from the location (chroma-pair loaders): waves that went on to the thresholds and the reference's
-// comparison.  A few percent of the waves of ordinary video, every wave of content with few luma levels, so slots as above
+// comparison.  A few percent of the waves of ordinary video, every wave of content with few luma levels
 // (ug_hip_dxt_encode_stats_alpha adds them up).
-__device__ unsigned long long g_exact_alpha_waves[kPairSlots * kPairSlotStride];
-__device__ __forceinline__ void count_exact_alpha()
-{
-        if ((int) threadIdx.x == __builtin_amdgcn_readfirstlane((int) threadIdx.x)) {
-                const uint32_t slot = ((blockIdx.x + 17u * blockIdx.y + 101u * blockIdx.z) * 4u + threadIdx.y) & (kPairSlots - 1);
-                atomicAdd(&g_exact_alpha_waves[slot * kPairSlotStride], 1ull);
-        }
-}
+__device__ unsigned long long g_exact_alpha_waves[kCounterWords];
+__device__ __forceinline__ void count_exact_alpha() { count_slotted(g_exact_alpha_waves, 1ull); }
 // DXT5-YCoCg alpha stage, chroma pairs: the certificate of the count taken from the location (derived at the stage),
 //   eps = kAlphaEpsFixed + kAlphaEpsRange / range,   in steps of range / 7
 constexpr float kAlphaEpsFixed = 2.2e-6f, kAlphaEpsRange = 5.7e-6f;
@@ -1045,11 +1042,12 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                 // projection within 0.05 eps of the one formed in double, and the projection margin within 0.04 eps of 9 H / vv).  A clamped s
                 // (a pixel beyond an end of the segment) has dist = 0: decided.  An exact tie has |dist| = 1/2 and is never certified:
                 // at 5/6 the reference's strict > gives c1 and RN could give either.  Flat blocks are certified as they are: their
-                // word is replaced below.  A wave that holds an uncertified block (a pixel next to a bisector: smooth gradients put some
-                // there) does what the stage did before the index came from the projection: it writes the rows (A, B), finds the zone of each
-                // pair from RN(clamp(3 s - 1/2, 0, 2)) (the constants of the row paragraph above, formed on that side only) and evaluates the
-                // reference's two distances for every pixel of all its blocks, operands and order as in the reference.  These fma only
-                // locate; no result of theirs is an operation of the reference.
+                // word is replaced below.  A wave that holds an uncertified pair (a pixel next to a bisector: smooth gradients put some
+                // there) does for that pair what the stage did before the index came from the projection: it finds the pair's zone from
+                // RN(clamp(3 s - 1/2, 0, 2)) (the constants of the row paragraph above, formed on that side only), takes the zone's palette pair
+                // (A, B) and evaluates the reference's two distances for the pair's two pixels, operands and order as in the reference; every
+                // certified pair of the wave keeps the projection's index (the slot form, at the side).  These fma only locate; no result
+                // of theirs is an operation of the reference.
                 const float vx = cx[1] - cx[0], vy = cy[1] - cy[0];
                 const float vv = vx * vx + vy * vy;
                 const float e0 = fmaxf(fmaxf(mxCo, cx[0]), cx[1]) - fminf(fminf(mnCo, cx[0]), cx[1]);
@@ -1100,33 +1098,62 @@ __device__ __forceinline__ uint4 encode_dxt5ycocg(Px16 &p, const IndexTables &ta
                                 } else {
                                         // The empty asm keeps this a real branch (see the alpha stage's fallback); vv passes through it so that
                                         // this side forms its own reciprocal and constants: nothing of it is computed ahead of the branch.
-                                        float vw = vv;
-                                        asm volatile("; per-pixel distances" : "+v"(vw) :: "memory");
+                                        // The slot form.  The certificate is per pair: `worst` is the maximum over the pairs and eps belongs to the
+                                        // block, so every pair with |dist| < 1/2 - eps keeps the projection's index whatever the rest of the wave
+                                        // holds.  The side forms the projection's word as the certified branch does, finds per pair slot k the lanes
+                                        // whose pair k is uncertified (the main line's operations on the main line's operands: the same bits, so
+                                        // the slots' masks add up to the complement of `certain`) and, behind a scalar branch per slot, gives the
+                                        // two pixels of that slot the reference's distances; only the uncertified lanes take the result.
+                                        // The word and the threshold pass through the asm as well: the side's arithmetic starts behind the branch.
+                                        float vw = vv, thr = 0.5f - eps;
+                                        uint32_t pw = jw;
+                                        asm volatile("; per-pixel distances" : "+v"(vw), "+v"(pw), "+v"(thr) :: "memory");
                                         const float off = side_offset<PAIRS>();
                                         count_exact_pair();
-                                        write_rows(cx[0], cy[0], cx[1], cy[1], cx[2], cy[2], cx[3], cy[3]);
-                                        const float inv = 1.5f * __builtin_amdgcn_rcpf(vw);
+                                        pw -= index_bias_sum(8, 4);
+                                        pw |= pw << 2;
+                                        const uint32_t p1 = (pw >> 1) & 0x55555555u;
+                                        w_cidx = p1 | (((pw ^ p1) & 0x55555555u) << 1);
+                                        const float rvw = __builtin_amdgcn_rcpf(vw);
+                                        const float la = vx * rvw, lb = vy * rvw;
+                                        const float la2 = la * 0.5f, lb4 = lb * 0.25f;
+                                        const float lc = __builtin_fmaf(kOffset - cx[0], la, (kOffset - cy[0]) * lb);
+                                        // the zone constants of the row paragraph above, as this side always formed them
+                                        const float inv = 1.5f * rvw;
                                         const float za = vx * inv, zb = vy * inv;
                                         const float zc = __builtin_fmaf(-cx[0], za, __builtin_fmaf(-cy[0], zb, -0.25f));
-                                        uint32_t zones = 0, open = 0; // 2-bit zone per pixel; the open comparison's result, one bit per pixel
+                                        const lanemask_t notflat = ~LANEMASK(flat);
+                                        uint32_t evaluated = 0; // wave-uniform
 #pragma unroll
                                         for (int i = 14; i >= 0; i -= 2) {
-                                                const float s = clamp01(__builtin_fmaf(co_of<PAIRS>(Co[i], off), za, __builtin_fmaf(cg_of<PAIRS>(Cg[i], off), zb, zc)));
-                                                zones = (zones << 4) + __float_as_uint(__builtin_fmaf(s, 2.0f, kIndexBias)); // kIndexBits + 0, 1, 2
-                                        }
-                                        zones -= index_bias_sum(8, 4);
-                                        zones |= zones << 2; // pair j's zone sits in bits 4j, 4j + 1 = the field of pixel 2j: copy it to pixel 2j + 1's
+                                                const float s = clamp01(__builtin_fmaf(Co[i], la2, __builtin_fmaf(Cg[i], lb4, lc)));
+                                                const float r = __builtin_fmaf(s, 3.0f, kIndexBias);
+                                                const float dist = __builtin_fmaf(s, 3.0f, kIndexBias - r);
+                                                const bool uncertified = !(fabsf(dist) < thr) & !flat;
+                                                if ((LANEMASK(!(fabsf(dist) < thr)) & notflat) != 0) { // scalar, on the comparison's own lane mask
+                                                        asm volatile("; pair slot" ::: "memory"); // a real branch, as above
+                                                        evaluated++;
+                                                        const float co0 = co_of<PAIRS>(Co[i], off), cg0 = cg_of<PAIRS>(Cg[i], off); // the reference's pixels
+                                                        const float co1 = co_of<PAIRS>(Co[i + 1], off), cg1 = cg_of<PAIRS>(Cg[i + 1], off);
+                                                        const float sz = clamp01(__builtin_fmaf(co0, za, __builtin_fmaf(cg0, zb, zc)));
+                                                        const uint32_t zone = __float_as_uint(__builtin_fmaf(sz, 2.0f, kIndexBias)) - kIndexBits; // 0, 1, 2
+                                                        // the palette pair whose bisector crosses the zone: (c0, c2), (c2, c3), (c1, c3)
+                                                        const bool z0 = zone == 0u, z1 = zone == 1u;
+                                                        const float qx = z0 ? cx[0] : z1 ? cx[2] : cx[1], qy = z0 ? cy[0] : z1 ? cy[2] : cy[1];
+                                                        const float qz = z0 ? cx[2] : cx[3], qw = z0 ? cy[2] : cy[3];
+                                                        uint32_t nib = 0;
 #pragma unroll
-                                        for (int i = 15; i >= 0; i--) { // the pixel's zone sits in bits 2 i, 2 i + 1; a row is 64 float4
-                                                const float4 q = *(const float4 *) ((const char *) tc + (((zones >> (2 * i)) & 3u) << 10));
-                                                const float co = co_of<PAIRS>(Co[i], off), cg = cg_of<PAIRS>(Cg[i], off); // the reference's pixel, formed on this side only
-                                                const float ax = co - q.x, ay = cg - q.y, bx = co - q.z, by = cg - q.w;
-                                                const float da = ax * ax + ay * ay, db = bx * bx + by * by; // glsl:231-235, same operation order
-                                                open = shift_in(open, LANEMASK(da > db));
+                                                        for (int h = 1; h >= 0; h--) {
+                                                                const float co = h ? co1 : co0, cg = h ? cg1 : cg0;
+                                                                const float ax = co - qx, ay = cg - qy, bx = co - qz, by = cg - qw;
+                                                                const float da = ax * ax + ay * ay, db = bx * bx + by * by; // glsl:231-235, same operation order
+                                                                const uint32_t c = da > db ? 1u : 0u, k0 = zone & 1u, k1 = zone >> 1;
+                                                                nib = (nib << 2) | ((k0 & c) | k1) | ((k0 | c) << 1); // k = 0: 2 b2; 1: 2 + b4; 2: 1 + 2 b3
+                                                        }
+                                                        w_cidx = uncertified ? (w_cidx & ~(0xfu << (2 * i))) | (nib << (2 * i)) : w_cidx;
+                                                }
                                         }
-                                        const uint32_t c = spread16(open);
-                                        const uint32_t k0 = zones & 0x55555555u, k1 = (zones >> 1) & 0x55555555u;
-                                        w_cidx = ((k0 & c) | k1) | ((k0 | c) << 1);
+                                        count_pair_slots(evaluated);
                                 }
                         } else {
                                 write_rows(cx[0], cy[0], cx[1], cy[1], cx[2], cy[2], cx[3], cy[3]);
@@ -1702,19 +1729,31 @@ int ug_hip_time_dxt_encode(ug_pixfmt_t in, ug_dxt_t out, const void *src, void *
 } // extern "C"
 
 // Diagnostics: waves of this process's ug_hip_dxt_encode* launches on the current device that took the full form of an index stage
+// the sum over the slots of one counter, `offset` bytes into its symbol
+static int sum_slotted(const void *symbol, size_t offset, unsigned long long *sum)
+{
+        static unsigned long long lines[kCounterWords]; // (the callers synchronise the device: diagnostics, one caller at a time)
+        UG_HIP_TRY(hipMemcpyFromSymbol(lines, symbol, sizeof lines, offset));
+        *sum = 0;
+        for (int i = 0; i < kPairSlots; i++) *sum += lines[i * kPairSlotStride];
+        return UG_HIP_SUCCESS;
+}
 extern "C" int ug_hip_dxt_encode_stats(unsigned long long full_form_waves[2], int reset)
 {
         UG_HIP_TRY(hipDeviceSynchronize());
         if (full_form_waves) {
-                UG_HIP_TRY(hipMemcpyFromSymbol(full_form_waves, HIP_SYMBOL(g_full_form_waves), 2 * sizeof(unsigned long long)));
+                for (int which = 0; which < 2; which++) {
+                        const int rc = sum_slotted(HIP_SYMBOL(g_full_form_waves), which * sizeof(unsigned long long[kCounterWords]), &full_form_waves[which]);
+                        if (rc != UG_HIP_SUCCESS) return rc;
+                }
         }
         if (reset) {
-                const unsigned long long zero[2] = { 0, 0 };
-                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_full_form_waves), zero, sizeof zero));
-                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_cov_waves), zero, sizeof zero[0]));
-                static const unsigned long long no_pairs[kPairSlots * kPairSlotStride] = {};
-                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_pair_waves), no_pairs, sizeof no_pairs));
-                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_alpha_waves), no_pairs, sizeof no_pairs));
+                static const unsigned long long none[2][kCounterWords] = {};
+                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_full_form_waves), none, sizeof none));
+                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_cov_waves), none, sizeof none[0]));
+                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_pair_waves), none, sizeof none[0]));
+                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_pair_slot_evaluations), none, sizeof none[0]));
+                UG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_exact_alpha_waves), none, sizeof none[0]));
         }
         return UG_HIP_SUCCESS;
 }
@@ -1727,12 +1766,25 @@ extern "C" int ug_hip_dxt_encode_stats_ex(unsigned long long *counts, int n, int
         unsigned long long all[4] = { 0, 0, 0, 0 };
         UG_HIP_TRY(hipDeviceSynchronize());
         if (n > 0) {
-                UG_HIP_TRY(hipMemcpyFromSymbol(all, HIP_SYMBOL(g_full_form_waves), 2 * sizeof all[0]));
-                UG_HIP_TRY(hipMemcpyFromSymbol(all + 2, HIP_SYMBOL(g_exact_cov_waves), sizeof all[0]));
-                static unsigned long long pairs[kPairSlots * kPairSlotStride]; // (this function synchronises the device: diagnostics, one caller at a time)
-                UG_HIP_TRY(hipMemcpyFromSymbol(pairs, HIP_SYMBOL(g_exact_pair_waves), sizeof pairs));
-                for (int i = 0; i < kPairSlots; i++) all[3] += pairs[i * kPairSlotStride];
+                int rc = ug_hip_dxt_encode_stats(all, 0);
+                if (rc == UG_HIP_SUCCESS) rc = sum_slotted(HIP_SYMBOL(g_exact_cov_waves), 0, &all[2]);
+                if (rc == UG_HIP_SUCCESS) rc = sum_slotted(HIP_SYMBOL(g_exact_pair_waves), 0, &all[3]);
+                if (rc != UG_HIP_SUCCESS) return rc;
                 for (int i = 0; i < n; i++) counts[i] = all[i];
+        }
+        return reset ? ug_hip_dxt_encode_stats(nullptr, 1) : UG_HIP_SUCCESS;
+}
+
+// Of the waves of counts[3] above: the pair slots that were evaluated.  The side of the colour stage's projection keeps the projection's
+// index for every certified pair and forms the reference's two distances only for the pixels of a pair slot (0 .. 7) in which some lane
+// of the wave holds an uncertified pair; *slot_evaluations (may be NULL) receives the number of such (wave, slot) evaluations, between
+// 1 and 8 for every wave that counts[3] counted.  Any reset clears this counter too.
+extern "C" int ug_hip_dxt_encode_stats_pair_slots(unsigned long long *slot_evaluations, int reset)
+{
+        UG_HIP_TRY(hipDeviceSynchronize());
+        if (slot_evaluations) {
+                const int rc = sum_slotted(HIP_SYMBOL(g_pair_slot_evaluations), 0, slot_evaluations);
+                if (rc != UG_HIP_SUCCESS) return rc;
         }
         return reset ? ug_hip_dxt_encode_stats(nullptr, 1) : UG_HIP_SUCCESS;
 }
@@ -1744,11 +1796,8 @@ extern "C" int ug_hip_dxt_encode_stats_alpha(unsigned long long *exact_waves, in
 {
         UG_HIP_TRY(hipDeviceSynchronize());
         if (exact_waves) {
-                static unsigned long long slots[kPairSlots * kPairSlotStride]; // (diagnostics, one caller at a time, as above)
-                UG_HIP_TRY(hipMemcpyFromSymbol(slots, HIP_SYMBOL(g_exact_alpha_waves), sizeof slots));
-                unsigned long long sum = 0;
-                for (int i = 0; i < kPairSlots; i++) sum += slots[i * kPairSlotStride];
-                *exact_waves = sum;
+                const int rc = sum_slotted(HIP_SYMBOL(g_exact_alpha_waves), 0, exact_waves);
+                if (rc != UG_HIP_SUCCESS) return rc;
         }
         return reset ? ug_hip_dxt_encode_stats(nullptr, 1) : UG_HIP_SUCCESS;
 }

@@ -97,6 +97,7 @@ SYMBOLS = {
     "ug_hip_dxt_encode_stats": (_i, [C.POINTER(C.c_ulonglong), _i]),
     "ug_hip_dxt_encode_stats_ex": (_i, [C.POINTER(C.c_ulonglong), _i, _i]),
     "ug_hip_dxt_encode_stats_alpha": (_i, [C.POINTER(C.c_ulonglong), _i]),
+    "ug_hip_dxt_encode_stats_pair_slots": (_i, [C.POINTER(C.c_ulonglong), _i]),
     "ug_hip_ldgm_stats": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "ug_hip_ldgm_create": (_i, [_i, _i, _i, _vp, _i, C.POINTER(_vp)]),
     "ug_hip_ldgm_destroy": (None, [_vp]),
